@@ -21,13 +21,29 @@ resident in HBM and step i runs on a new device copy of batch i mod B (new tenso
 host-to-device copy delivers them), so every per-batch structure -- kernel maps, tile / pair schedules, window
 plans, point<->pixel plans -- is rebuilt inside the timed region, as in training.
 
-Rank 0 prints ONE JSON line.  ``roofline`` is the dominant kernel group (SubMConv3d 64->64 k=3
-at 80k voxels: forward + input gradient + weight gradient), timed live with HIP events on the
-launch stream; ``cpu_baseline`` is the CPU oracle timed on the host cores on a bounded sample
-(rank 0, N=1 only); ``secondary`` (N=1 only) holds the LiDAR-only configs[1] step, the configs[4] step on one GPU
-(multi-sweep teacher scene, bf16 autocast), the KD step on 6 x 900x1600 images (SURVEY 8d "report both"; a child
-process with a bounded MIOpen search and its own timeout) and the KD step on the N>1 code path (DDP +
-SyncBatchNorm with a one-rank group) so the price of that path is visible at N = 1.
+Rank 0 prints ONE JSON line.  A plain run does only what that line's headline needs: it sets up, runs W untimed and
+K timed steps, writes the last step's outputs if ``--dump-outputs DIR`` is given, and prints the line.
+
+``--dump-outputs DIR`` (rank 0): after the timed steps, what the last timed step computed, as ``DIR/<name>.npy`` in float32
+(float64 for the loss): ``loss``, every floating-point tensor the model's forward returned (``output.<key path>``), and the
+trainable parameters after the optimizer step and their gradients of that step, flattened and concatenated in the
+optimizer's order (``params``, ``grads``).  An array of more than DUMP_ELEMENTS elements (or more than what is left of
+DUMP_BUDGET, the largest last) is written as a 1-D, seeded sample of that many at the same positions on every run; the
+log line lists what was sampled.  The batches and the initial weights come from fixed seeds, and the last timed step
+starts from the initial weights and a zero momentum (restored in front of it, initial_state_restorer), so what it computes
+depends only on the arguments: two runs, or two builds, with the same arguments can be compared output for output.
+In such a run ``final_loss`` is the loss at the initial weights and ``ms_per_step`` includes that restore and the rebuild
+of the weight fragments it causes in the last step (4-9 ms per step over K = 20): read the speed off a plain run.
+
+``--full`` adds the legs beyond the headline (each can still be dropped with its ``--no-*`` option).  ``roofline`` is
+the dominant kernel group (SubMConv3d 64->64 k=3 at 80k voxels: forward + input gradient + weight gradient), timed
+live with HIP events on the launch stream; ``cpu_baseline`` is the CPU oracle timed on the host cores on a bounded
+sample (rank 0, N=1 only); ``secondary`` (N=1 only) holds the LiDAR-only configs[1] step, the configs[4] step on one
+GPU (multi-sweep teacher scene, bf16 autocast), the KD step on 6 x 900x1600 images (SURVEY 8d "report both"; a child
+process with a bounded MIOpen search and its own timeout), the KD step fed from pinned host memory and the KD step on
+the N>1 code path (DDP + SyncBatchNorm with a one-rank group) so the price of that path is visible at N = 1; and the
+frozen teacher's logits are checked bit for bit against the first step that ran the same batch
+(``config.teacher_deviating_steps``: null in a plain run).  ``--kernel-only`` runs the roofline leg alone.
 """
 import argparse
 import json
@@ -36,6 +52,7 @@ import socket
 import subprocess
 import sys
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
@@ -80,7 +97,15 @@ def parse():
                     help='distinct resident batches rotated through the timed loop (every step gets fresh tensors)')
     ap.add_argument('--child-timeout', type=int, default=360, help='seconds a secondary child process may take')
     ap.add_argument('--cpu-sample-voxels', type=int, default=20000)
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='also run the secondary workloads, the roofline legs, the CPU baseline and the teacher bit-check '
+                         '(a plain run times the headline step only)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the last timed step computed to DIR/<name>.npy (rank 0)')
+    a = ap.parse_args()
+    if a.kernel_only and a.dump_outputs:
+        ap.error('--dump-outputs needs the timed step; --kernel-only runs none')
+    return a
 
 
 # ----------------------------------------------------------------------------------- launcher
@@ -502,7 +527,7 @@ def child_leg(args, extra_argv, extra_env, workload_note):
     """One bench leg in a fresh child process with its own environment and a timeout; returns the secondary entry."""
     cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--workload', args.workload, '--voxels', str(args.voxels),
            '--cr', str(args.cr), '--cr-t', str(args.cr_t), '--dtype', args.dtype, '--batches', str(args.batches),
-           '--no-secondary', '--no-cpu-baseline', '--no-roofline'] + extra_argv
+           '--full', '--no-secondary', '--no-cpu-baseline', '--no-roofline'] + extra_argv
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
     env.update(extra_env)
     t0 = time.perf_counter()
@@ -519,6 +544,85 @@ def child_leg(args, extra_argv, extra_env, workload_note):
                 'workload': workload_note}
 
 
+# ------------------------------------------------------------------------- library kernel builds
+# MIOpen builds the kernels of a convolution the first time a process runs it and keeps them in the user's cache; with a cold
+# cache, the KD step's ~60 builds are ~35 s of its first step, one after the other.  These children (one GPU process each)
+# run the camera backbone's convolutions -- forward, input gradient where the step takes one, weight gradient -- and the
+# LiDAR -> camera fusion blocks, a share each, while the parent sets up and warms up; the parent's warm-up finds the kernels they have built and builds the rest
+# itself.  Shapes come from a pass of the same module on the meta device.
+PREWARM_CHILD = r"""
+import copy, sys
+sys.path.insert(0, %(root)r)
+import torch
+import torch.nn.functional as F
+from bench import kd_model
+share, shares, hw, dtype = %(share)d, %(shares)d, %(hw)r, getattr(torch, %(dtype)r)
+student = kd_model(%(cr)r, %(cr_t)r).model_s          # the model the step builds (on the CPU: shapes only)
+cam = copy.deepcopy(student.pix_branch).to('meta').train()
+probs = set()
+for m in cam.modules():
+    if isinstance(m, torch.nn.Conv2d):
+        m.register_forward_pre_hook(lambda m, a: probs.add((tuple(a[0].shape), tuple(m.weight.shape), m.stride, m.padding,
+                                                            m.dilation, m.groups, m.bias is not None, a[0].requires_grad)))
+stage_hw = {}
+for s in range(1, 5):
+    getattr(cam, 'layer%%d' %% s)[-1].register_forward_hook(lambda m, a, y, s=s: stage_hw.__setitem__(s, tuple(y[0].shape[-2:])))
+cam(torch.empty(6, 3, *hw, device='meta'))
+for xs, ws, stride, padding, dilation, groups, bias, needs_dx in sorted(probs)[share::shares]:
+    x = torch.randn(xs, device='cuda', dtype=dtype, requires_grad=needs_dx)      # (no input gradient for the images)
+    w = torch.randn(ws, device='cuda', dtype=dtype, requires_grad=True)
+    b = torch.zeros(ws[0], device='cuda', dtype=dtype, requires_grad=True) if bias else None
+    y = F.conv2d(x, w, b, stride, padding, dilation, groups)
+    y.backward(torch.ones_like(y))
+# the LiDAR -> camera fusion block of stage j + 1 (1x1 convolutions with bias over [6, C, h, w]: the scattered point
+# features and the stage's image features), on the children with the fewest backbone convolutions
+for j, blk in enumerate(student.l2c_fusion_blocks):
+    if (shares - 1 - j) %% shares == share:
+        blk = blk.cuda().train()
+        pts = torch.randn(6, blk.l2c_ai_layer.pc, *stage_hw[j + 1], device='cuda', requires_grad=True)
+        img = torch.randn(6, blk.l2c_ai_layer.ic, *stage_hw[j + 1], device='cuda', requires_grad=True)
+        with torch.autocast('cuda', dtype=torch.bfloat16, enabled=dtype is torch.bfloat16):
+            y = blk(pts, img)[0]
+        y.float().sum().backward()
+torch.cuda.synchronize()
+"""
+
+
+def prewarm_start(args, shares=8):
+    """The children above for a one-GPU KD run (6 cameras of --image-hw, the run's dtype); join with prewarm_join, stop
+    with prewarm_stop."""
+    if args.workload != 'kd' or args.gpus != 1 or args.kernel_only:
+        return []
+    dtype = 'bfloat16' if args.dtype == 'bf16' else 'float32'
+    code = lambda i: PREWARM_CHILD % {'root': ROOT, 'share': i, 'shares': shares, 'cr': args.cr, 'cr_t': args.cr_t,
+                                      'hw': tuple(args.image_hw), 'dtype': dtype}
+    return [subprocess.Popen([sys.executable, '-c', code(i)], stdout=subprocess.DEVNULL, stderr=subprocess.PIPE,
+                             start_new_session=True) for i in range(shares)]
+
+
+def prewarm_stop(procs):
+    """Kill the children still running (the parent failed, or one of them did)."""
+    for p in procs:
+        if p.poll() is None:
+            os.killpg(p.pid, 9)
+            p.wait()
+
+
+def prewarm_join(procs, timeout_s=120):
+    """Wait for the children.  One that fails or runs out of time stops the benchmark: it may have left the GPU in a
+    fault, and nothing more is started on it."""
+    deadline = time.monotonic() + timeout_s
+    for p in procs:
+        try:
+            _, err = p.communicate(timeout=max(1.0, deadline - time.monotonic()))
+        except subprocess.TimeoutExpired:
+            prewarm_stop(procs)
+            raise SystemExit('kernel pre-build child did not finish in %d s' % timeout_s)
+        if p.returncode:
+            prewarm_stop(procs)
+            raise SystemExit('kernel pre-build child exited with %d: %s' % (p.returncode, err.decode(errors='replace')[-1000:]))
+
+
 def log(msg):
     sys.stderr.write('[bench %.1fs] %s\n' % (time.perf_counter() - _T0, msg))
     sys.stderr.flush()
@@ -528,14 +632,23 @@ _T0 = time.perf_counter()
 
 
 # --------------------------------------------------------------------------------- workloads
-def build_step(args, rank, workload, image_hw, sweeps=None, dtype=None, voxels=None, cr=None, cr_t=None, h2d=False):
+def kd_model(cr, cr_t):
+    """The KD model of the benchmark (student SwiftNet18 + SPVCNN+SphereFormer at width cr, teacher at cr_t), on the CPU."""
+    from u2mkd_amd import kd as KD, lidar
+    sp = {k: v for k, v in lidar.spformer_kwargs().items() if k not in ('cr', 'in_channel', 'num_classes')}
+    return KD.TSDFull(cr=cr, cr_t=cr_t, in_channel=4, in_channel_t=4, num_classes=17, spformer=sp)
+
+
+def build_step(args, rank, workload, image_hw, sweeps=None, dtype=None, voxels=None, cr=None, cr_t=None, h2d=False, watch=True):
     """(step closure, points per step on this rank, description).  sweeps / dtype / voxels / cr / cr_t: the configs[4]
     variant (multi-sweep teacher scene of `voxels` points, bf16 autocast with bf16 storage, the `_B` widths cr 2.0 /
-    cr_t 2.0 of configs/nuscenes/train/spformer_tsd_full_ours_star_B.yaml:34-36)."""
+    cr_t 2.0 of configs/nuscenes/train/spformer_tsd_full_ours_star_B.yaml:34-36).  watch: keep the KD teacher's logits
+    of every step for the bit-check (build_step.watch).  The closure carries the model (``step.model``) and its
+    optimizer (``step.opt``) for --dump-outputs."""
     import torch
     from u2mkd_amd import lidar, train as T
     from u2mkd_amd.synth import synth_batch, synth_kd_batch
-    torch.manual_seed(0)
+    torch.manual_seed(0)        # the CPU and every GPU generator: the same initial weights and dropout / DropPath masks every run
     build_step.watch = None
     amp = 'bf16' if (dtype or args.dtype) == 'bf16' else False
     n_vox = voxels or args.voxels
@@ -558,11 +671,10 @@ def build_step(args, rank, workload, image_hw, sweeps=None, dtype=None, voxels=N
             counter[0] += 1
             nxt[0] = tuple(t.clone() for t in res[counter[0] % n_batches])
             return runner(feats, coords, labels, prefetch=nxt[0][:2] if prefetch else None)
+        step.model, step.opt = model, runner.opt
         return step, res[0][0].shape[0], desc
-    from u2mkd_amd import kd as KD
-    sp = {k: v for k, v in lidar.spformer_kwargs().items() if k not in ('cr', 'in_channel', 'num_classes')}
     cr, cr_t = cr or args.cr, cr_t or args.cr_t
-    model = KD.TSDFull(cr=cr, cr_t=cr_t, in_channel=4, in_channel_t=4, num_classes=17, spformer=sp).cuda()
+    model = kd_model(cr, cr_t).cuda()
     runner = T.KDStep(model, num_epochs=50, batch_size=1, amp=amp)
     runner.train_mode()
     n_batches = max(1, args.batches)
@@ -589,11 +701,12 @@ def build_step(args, rank, workload, image_hw, sweeps=None, dtype=None, voxels=N
     counter = [0]
     nxt = [None]
     prefetch = os.environ.get('U2MKD_PREFETCH_GEOMETRY', '1') != '0'
-    watch = T.TeacherWatch(model.model_t)       # (one clone of the teacher's logits per step, on its stream: ~5 MB)
+    watch = T.TeacherWatch(model.model_t) if watch else None      # (one clone of the teacher's logits per step, on its stream: ~5 MB)
     build_step.watch = watch
 
     def step():
-        watch.key = counter[0] % n_batches
+        if watch is not None:
+            watch.key = counter[0] % n_batches
         # a fresh device copy of the next resident batch: new tensor objects every step (what the data loader's
         # host-to-device copy hands the reference's _prepare_input, core/nusc_trainers.py:257-279), so nothing cached
         # on a batch tensor -- point<->pixel plans, kernel maps, schedules -- survives from an earlier step.
@@ -605,25 +718,33 @@ def build_step(args, rank, workload, image_hw, sweeps=None, dtype=None, voxels=N
         nxt[0] = dict(fresh(resident[counter[0] % n_batches]), _key=counter[0] % n_batches) if prefetch else None
         return runner(d, prefetch=nxt[0])
     step.runner = runner
+    step.model, step.opt = model, runner.opt
     return step, n_pts, desc
 
 
-def timed_run(step, warmup, steps, world):
+def timed_run(step, warmup, steps, world, after_warmup=None, before_last=None):
     """W untimed steps, then exactly K steps between barrier + synchronize on both sides; the
-    MAX over ranks."""
+    MAX over ranks.  after_warmup: called behind the warm-up steps, before the timed region;
+    before_last: called in front of the last timed step (inside the timed region)."""
     import torch
     import torch.distributed as dist
     from u2mkd_amd import distributed as D
+    tw = time.perf_counter()
     for _ in range(warmup):
         step()
+    if after_warmup is not None:
+        after_warmup()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
+    timed_run.warmup_s = time.perf_counter() - tw       # (first-call library work -- kernel builds, algorithm picks -- lands here)
     D.collective_counts(reset=True)
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
     marks[0].record()
     t0 = time.perf_counter()
     for i in range(steps):
+        if before_last is not None and i == steps - 1:
+            before_last()
         loss = step()
         marks[i + 1].record()       # end of step i on the stream the step's last work (optimizer) was queued on; no host wait
     timed_run.host_issue_ms = (time.perf_counter() - t0) / steps * 1e3     # the host's share: time to QUEUE a step (its own waits included)
@@ -641,6 +762,83 @@ def timed_run(step, warmup, steps, world):
                              'gradient_all_reduce_per_step': cc.get('gradient_buckets_last_pass')}
     timed_run.per_rank = (D.min_over_ranks(dt), D.max_over_ranks(dt))     # fastest / slowest rank of this timed region
     return timed_run.per_rank[1], float(loss.detach())
+
+
+# --------------------------------------------------------------------------------- --dump-outputs
+DUMP_ELEMENTS = 1 << 21         # elements per written array; a larger array is written as a seeded sample of this many
+DUMP_BUDGET = 14 << 20          # elements over all arrays (59 MB of float32): the largest arrays are sampled down to what is left
+
+
+def capture_output(model, call):
+    """Forward hook on ``model`` that keeps the output of its ``call``-th forward (the last timed step's: one forward of the
+    model per step).  Only that output is held, so the steps before it run as without the hook."""
+    box = {'calls': 0}
+
+    def hook(module, inputs, output):
+        box['calls'] += 1
+        if box['calls'] == call:
+            box['out'] = output
+    box['handle'] = model.register_forward_hook(hook)
+    return box
+
+
+def _float_leaves(obj, prefix):
+    """(name, tensor) of every floating-point tensor in a nest of dicts / lists / tuples, in a fixed order."""
+    import torch
+    if torch.is_tensor(obj):
+        return [(prefix, obj)] if obj.is_floating_point() else []
+    if isinstance(obj, dict):
+        return [kv for k in sorted(obj, key=str) for kv in _float_leaves(obj[k], '%s.%s' % (prefix, k))]
+    if isinstance(obj, (list, tuple)):
+        return [kv for i, v in enumerate(obj) for kv in _float_leaves(v, '%s.%d' % (prefix, i))]
+    return []
+
+
+def initial_state_restorer(opt):
+    """For --dump-outputs: a closure that puts the trainable parameters back to their values at this call and zeroes the
+    optimizer's momentum (a zero buffer gives the first step's update), run in front of the last timed step.  Without it
+    that step would start from W + K - 1 steps of training at lr 0.24, which amplify the run-to-run rounding of library
+    kernels (MIOpen's split reductions, NOTES N6) into O(1) differences; from the initial state, what the step computes
+    depends only on the arguments, up to that rounding.  The restore (one multi-tensor copy and one multi-tensor zero) runs
+    inside the timed region, once; the sparse convolutions' weight fragments are stamped with the weight's version
+    (torchsparse/nn/functional.py) and are rebuilt from the restored values in that step."""
+    import torch
+    params = [p for g in opt.param_groups for p in g['params']]
+    init = [p.detach().clone() for p in params]
+
+    def restore():
+        with torch.no_grad():
+            torch._foreach_copy_(params, init)
+            bufs = [st['momentum_buffer'] for st in (opt.state.get(p, {}) for p in params) if st.get('momentum_buffer') is not None]
+            if bufs:
+                torch._foreach_zero_(bufs)
+    return restore
+
+
+def dump_outputs(dirname, loss, output, opt):
+    """Write the last timed step's results (module docstring, --dump-outputs); returns {name: elements written, or
+    'shape -> sample' for a sampled array}."""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()
+    params = [p for g in opt.param_groups for p in g['params']]
+    with torch.no_grad():
+        arrays = [('params', torch.cat([p.detach().reshape(-1).float() for p in params])),
+                  ('grads', torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float()
+                                       for p in params]))] + _float_leaves(output, 'output')
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, 'loss.npy'), np.array([loss], dtype=np.float64))
+    written, left = {'loss': 1}, DUMP_BUDGET
+    for name, t in sorted(arrays, key=lambda nt: (nt[1].numel(), nt[0])):      # smallest first: they are written whole
+        t = t.detach()
+        k = min(t.numel(), DUMP_ELEMENTS, left)
+        written[name] = k if k == t.numel() else '%s -> %d' % (list(t.shape), k)
+        if k < t.numel():           # a 1-D sample at the same positions whenever the array has the same name and size
+            idx = np.random.default_rng(zlib.crc32(name.encode())).choice(t.numel(), k, replace=False)
+            t = t.reshape(-1)[torch.from_numpy(np.sort(idx)).to(t.device)]
+        np.save(os.path.join(dirname, name + '.npy'), t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy())
+        left -= k
+    return written
 
 
 def run_rank(args):
@@ -669,12 +867,29 @@ def run_rank(args):
         raise SystemExit(f'--gpus {args.gpus} but WORLD_SIZE={world}')
     result = {}
     if not args.kernel_only:
-        step, n_pts, desc = build_step(args, rank, args.workload, args.image_hw, h2d=args.h2d)
-        if args.h2d:
-            desc += ' -- every step starts from a PINNED HOST batch (host-to-device copies inside the timed region)'
-        log('model built, scene resident; warm-up')
-        dt, loss = timed_run(step, args.warmup, args.steps, world)
+        prewarm = prewarm_start(args)
+        try:
+            step, n_pts, desc = build_step(args, rank, args.workload, args.image_hw, h2d=args.h2d, watch=args.full)
+            if args.h2d:
+                desc += ' -- every step starts from a PINNED HOST batch (host-to-device copies inside the timed region)'
+            setup_s = time.perf_counter() - _T0
+            log('model built, scene resident; warm-up')
+            # --dump-outputs: every rank restores (gradient averaging and SyncBatchNorm see one consistent state), rank 0 writes
+            restore = initial_state_restorer(step.opt) if args.dump_outputs else None
+            box = capture_output(step.model, args.warmup + args.steps) if args.dump_outputs and rank == 0 else None
+            # (the pre-build children are joined behind the warm-up: a kernel they have not built yet, the warm-up builds itself)
+            dt, loss = timed_run(step, args.warmup, args.steps, world, after_warmup=lambda: prewarm_join(prewarm),
+                                 before_last=restore)
+        finally:
+            prewarm_stop(prewarm)
         log('timed region done: %.3f s' % dt)
+        if box is not None:
+            box['handle'].remove()
+            if box['calls'] != args.warmup + args.steps:
+                raise SystemExit('--dump-outputs: the model ran %d forwards in %d steps' % (box['calls'], args.warmup + args.steps))
+            written = dump_outputs(args.dump_outputs, loss, box.pop('out'), step.opt)
+            log('outputs of the last step written to %s: %s (that step started from the initial weights: final_loss is its '
+                'loss, and ms_per_step includes the restore in front of it)' % (args.dump_outputs, json.dumps(written)))
         teacher_bad, teacher_compared = (build_step.watch.deviating_steps() if getattr(build_step, 'watch', None) else (None, None))
         result.update({
             'metric': METRIC, 'value': round(world * n_pts * args.steps / dt, 1), 'unit': 'points/s', 'n_gpus': world,
@@ -693,6 +908,8 @@ def run_rank(args):
                                                  'region (the voxel sets / kernel maps of batch i+1 during step i, between '
                                                  'its forward and backward: one geometry pass per step)' % args.batches,
                        'final_loss': round(loss, 5),
+                       # wall time before the timed steps: process start -> model built and batches resident, then the W warm-up steps
+                       'setup_wall_s': round(setup_s, 1), 'warmup_wall_s': round(timed_run.warmup_s, 1),
                        # the frozen teacher is a pure function of the batch: steps (warm-up + timed) whose teacher logits differ in
                        # any bit from the first step that ran the same resident batch (train.TeacherWatch; NOTES N9)
                        'teacher_deviating_steps': teacher_bad, 'teacher_steps_compared': teacher_compared,
@@ -717,7 +934,7 @@ def run_rank(args):
                             'ms_per_step_max_rank': round(timed_run.per_rank[1] / args.steps * 1e3, 3)},
         })
         del step
-        if world == 1 and not args.no_secondary:
+        if world == 1 and args.full and not args.no_secondary:
             sec = {}
             torch.cuda.empty_cache()
             # (warm-up covers every rotated batch once: a batch's first step allocates, and a short leg then scatters by +-3 ms)
@@ -763,7 +980,7 @@ def run_rank(args):
 
     if rank == 0:
         from u2mkd_amd.synth import synth_batch
-        if not args.no_roofline:
+        if (args.full or args.kernel_only) and not args.no_roofline:
             coords = torch.from_numpy(synth_batch(args.voxels, 1, seed=1234)['coords']).cuda()
             result['roofline'] = roofline_leg(coords)
             log('roofline leg done')
@@ -773,7 +990,7 @@ def run_rank(args):
                 except Exception as e:      # never blocks the judged line
                     result['roofline_wide'] = {'error': '%s: %s' % (type(e).__name__, str(e)[:200])}
                 log('wide-layer roofline leg done')
-        if world == 1 and not args.no_cpu_baseline and not args.kernel_only:
+        if world == 1 and args.full and not args.no_cpu_baseline and not args.kernel_only:
             log('cpu baseline (child process)')
             result['cpu_baseline'] = cpu_baseline_leg(args)
         print(json.dumps(result), flush=True)

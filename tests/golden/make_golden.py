@@ -33,6 +33,29 @@ from oracle import spvcnn_ref as O         # noqa: E402
 from u2mkd_amd.synth import synth_batch    # noqa: E402
 
 
+PART_BYTES = 900_000      # raw bytes per fixture file: every committed file stays under 1 MiB
+
+
+def save_golden(path, **arrays):
+    """np.savez_compressed over as many files as it takes: ``<stem>.npz``, then ``<stem>.1.npz``, ``<stem>.2.npz`` ...,
+    each holding whole arrays of at most PART_BYTES in all (tests/test_kd_path.py reads them back as one mapping)."""
+    stem = path[:-len('.npz')]
+    i = 1
+    while os.path.exists('%s.%d.npz' % (stem, i)):      # continuation files of an earlier run: the reader would merge them
+        os.remove('%s.%d.npz' % (stem, i))
+        i += 1
+    parts, size = [{}], 0
+    for k, v in arrays.items():
+        v = np.asarray(v)
+        if parts[-1] and size + v.nbytes > PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][k] = v
+        size += v.nbytes
+    for i, part in enumerate(parts):
+        np.savez_compressed(path if i == 0 else '%s.%d.npz' % (stem, i), **part)
+
+
 def import_reference():
     ots.install()                                   # `import torchsparse` -> CPU oracle
     sys.modules.setdefault('torchvision', types.ModuleType('torchvision'))
@@ -247,7 +270,7 @@ def make_kd_golden(crit, cr=1.0, cr_t=1.0, tag='kd_cr10_3000', n_vox=1500, write
     total = ce_vox + ce_pix + 1.0 * kl + sum(out['stu']['mse_loss']) + 1.0 * feat
     total.backward()
     g = {n: p.grad for n, p in model.named_parameters() if p.grad is not None}
-    np.savez_compressed(
+    save_golden(
         os.path.join(HERE, tag + '.npz'), seed=np.int64(seed), selection=np.array(SELECTION_NOTE if len(seeds) > 1 or batches is not None else 'fixed seed'),
         x_vox=x_vox.detach().numpy(), x_pix=x_pix.detach().numpy(), x_vox_t=out['t']['x_vox'].numpy(),
         mse=np.array([float(m) for m in out['stu']['mse_loss']], dtype=np.float32),
@@ -385,6 +408,55 @@ def make_loader_kd_golden():
     make_kd_golden(_Crit(ignore_index=0), cr=0.5, cr_t=0.5, tag='kd_loader_cr05', write_keys=False, batches=cands)
 
 
+def make_pinned_goldens():
+    """The reference's side of the two CPU oracle tests that compare at fp32 round-off, evaluated under the pinned CPU
+    numerics of tests/pinned_cpu.py (`python tests/golden/make_golden.py pinned` runs this in a child process with them):
+    spformer_cr10_4000_pinned.npz (SPVCNN_SPFORMER on the scene of spformer_cr10_4000.npz) and
+    teacher_multisweep_cr10_6000_pinned.npz (the multi-sweep scene and seed of teacher_multisweep_cr10_6000.npz)."""
+    import copy
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import pinned_cpu
+    assert all(os.environ.get(k) == v for k, v in pinned_cpu.ENV.items()), 'run under tests/pinned_cpu.ENV'
+    from oracle.spformer_ref import default_spformer_kwargs
+    _, MixLovaszCrossEntropy = import_reference()
+    SPF = import_reference_spformer(1.0)
+    crit = MixLovaszCrossEntropy(ignore_index=0)
+    kw = default_spformer_kwargs(cr=1.0, drop_path_rate=0.0)
+    for k in ('cr', 'in_channel', 'num_classes'):
+        kw.pop(k)
+
+    def model():
+        # a fresh copy of the arguments per construction: the reference's constructor edits some of them in place
+        ref = O.fill_state_by_name(SPF(**copy.deepcopy(kw))).train()
+        ref.dropout.p = 0.0
+        return ref
+    b = synth_batch(2000, 2, seed=33)
+    feats, coords, labels = (torch.from_numpy(b[k]) for k in ('feats', 'coords', 'labels'))
+    ref = model()
+    out = ref({'lidar': ots.SparseTensor(feats.clone(), coords.clone())})['x_vox']
+    loss = crit(out, labels)
+    loss.backward()
+    grads = {n: p.grad for n, p in ref.named_parameters()}
+    blk = 'transformer_blocks.1.attn.'
+    np.savez_compressed(
+        os.path.join(HERE, 'spformer_cr10_4000_pinned.npz'),
+        logits=out.detach().numpy().astype(np.float32), loss=np.float32(loss.item()),
+        grad_tq=grads[blk + 'relative_pos_query_table'].numpy(),
+        grad_tv_sphere=grads[blk + 'relative_pos_value_table_sphere'].numpy(),
+        grad_qkv=grads[blk + 'qkv.weight'].numpy())
+    seed = int(np.load(os.path.join(HERE, 'teacher_multisweep_cr10_6000.npz'))['seed'])
+    b = synth_batch(3000, 2, seed=seed, sweeps=3)
+    feats, coords, labels, kf = (torch.from_numpy(b[x]) for x in ('feats', 'coords', 'labels', 'keyframe'))
+    torch.manual_seed(0)
+    with torch.no_grad():
+        out = model()({'lidar': ots.SparseTensor(feats.clone(), coords.clone())})['x_vox']
+        loss = crit(out[kf], labels[kf])
+    np.savez_compressed(
+        os.path.join(HERE, 'teacher_multisweep_cr10_6000_pinned.npz'),
+        logits=out.numpy().astype(np.float32), loss=np.float32(loss.item()), n_keyframe=np.int64(kf.sum()))
+    print('pinned goldens written')
+
+
 def main_kd_widths():
     """Only the KD fixtures at the shipped widths (`python tests/golden/make_golden.py kd`)."""
     _, MixLovaszCrossEntropy = import_reference()
@@ -407,6 +479,13 @@ if __name__ == '__main__':
         make_loader_kd_golden()
     elif len(sys.argv) > 1 and sys.argv[1] == 'teacher_ms':
         make_teacher_multisweep_golden()
+    elif len(sys.argv) > 1 and sys.argv[1] == 'pinned':
+        import subprocess
+        sys.path.insert(0, os.path.join(ROOT, 'tests'))
+        import pinned_cpu
+        subprocess.run([sys.executable, os.path.abspath(__file__), 'pinned_child'], env=dict(os.environ, **pinned_cpu.ENV), check=True)
+    elif len(sys.argv) > 1 and sys.argv[1] == 'pinned_child':
+        make_pinned_goldens()
     else:
         main()
         main_kd_widths()

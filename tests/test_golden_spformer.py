@@ -32,23 +32,36 @@ def _inputs():
     return tuple(torch.from_numpy(b[k]) for k in ('feats', 'coords', 'labels'))
 
 
-def test_oracle_spformer_matches_reference_class():
-    gold = np.load(os.path.join(G, 'spformer_cr10_4000.npz'))
-    feats, coords, labels = _inputs()
-    m = O.fill_state_by_name(R.SPVCNN_SPFORMER(**R.default_spformer_kwargs(cr=1.0, drop_path_rate=0.0))).train()
-    m.dropout.p = 0.0
-    out = m({'lidar': ots.SparseTensor(feats, coords)})['x_vox']
-    # same algorithm, same operation order; only the BLAS thread partition of the dense layers may differ
-    assert np.abs(out.detach().numpy() - gold['logits']).max() < 5e-5
-    loss = O.mix_lovasz_cross_entropy(out, labels)
-    assert abs(float(loss.detach()) - float(gold['loss'])) < 1e-6
-    loss.backward()
-    g = dict(m.named_parameters())
+ORACLE_STEP = r'''
+import numpy as np, torch
+from oracle import spformer_ref as R, spvcnn_ref as O, torchsparse_cpu as ots
+from u2mkd_amd.synth import synth_batch
+b = synth_batch(2000, 2, seed=33)
+feats, coords, labels = (torch.from_numpy(b[k]) for k in ('feats', 'coords', 'labels'))
+m = O.fill_state_by_name(R.SPVCNN_SPFORMER(**R.default_spformer_kwargs(cr=1.0, drop_path_rate=0.0))).train()
+m.dropout.p = 0.0
+out = m({'lidar': ots.SparseTensor(feats, coords)})['x_vox']
+loss = O.mix_lovasz_cross_entropy(out, labels)
+loss.backward()
+g = dict(m.named_parameters())
+np.savez(OUT, logits=out.detach().numpy(), loss=loss.detach().numpy(), grad_tq=g[%(blk)r + 'relative_pos_query_table'].grad.numpy(),
+         grad_tv_sphere=g[%(blk)r + 'relative_pos_value_table_sphere'].grad.numpy(), grad_qkv=g[%(blk)r + 'qkv.weight'].grad.numpy())
+'''
+
+
+def test_oracle_spformer_matches_reference_class(tmp_path):
+    """The oracle against the reference class, both evaluated under the pinned CPU numerics of tests/pinned_cpu.py
+    (spformer_cr10_4000_pinned.npz: make_golden.py pinned)."""
+    import pinned_cpu
+    gold = np.load(os.path.join(G, 'spformer_cr10_4000_pinned.npz'))
+    got = pinned_cpu.run(ORACLE_STEP % {'blk': BLK}, tmp_path / 'oracle.npz')
+    # same algorithm, same operation order, same CPU numerics
+    assert np.abs(got['logits'] - gold['logits']).max() < 5e-5
+    assert abs(float(got['loss']) - float(gold['loss'])) < 1e-6
     # gradients: CPU index_add_ accumulation order varies run to run -> not bit-stable; 1e-4 of the max
-    for name, key in (('relative_pos_query_table', 'grad_tq'), ('relative_pos_value_table_sphere', 'grad_tv_sphere'),
-                      ('qkv.weight', 'grad_qkv')):
-        a, b = g[BLK + name].grad.numpy(), gold[key]
-        assert np.abs(a - b).max() <= 1e-4 * np.abs(b).max(), name
+    for key in ('grad_tq', 'grad_tv_sphere', 'grad_qkv'):
+        a, b = got[key], gold[key]
+        assert np.abs(a - b).max() <= 1e-4 * np.abs(b).max(), key
 
 
 def test_spformer_state_dict_keys_match_reference():

@@ -179,14 +179,25 @@ def test_loader_fed_kd_step_matches_the_reference_golden(hip, tmp_path):
     _kd_golden_check(0.5, 0.5, 'kd_loader_cr05', None, batch_of, pix_row_rel=1e-5, grad_gate=5e-3)
 
 
+def _load_golden(fixture):
+    """A fixture with its continuation files (``<fixture>.1.npz`` ...: make_golden.save_golden) as one mapping."""
+    gold, i = {}, 0
+    while os.path.exists(os.path.join(G, fixture + ('.%d.npz' % i if i else '.npz'))):
+        with np.load(os.path.join(G, fixture + ('.%d.npz' % i if i else '.npz'))) as f:
+            gold.update(f)
+        i += 1
+    assert gold, fixture
+    return gold
+
+
 def _kd_golden_check(cr, cr_t, fixture, n_vox, batch_of=None, pix_row_rel=0.0, grad_gate=1e-3):
     from oracle.spvcnn_ref import fill_state_by_name
     from u2mkd_amd import kd, torchsparse as ts
-    gold = np.load(os.path.join(G, fixture + '.npz'))
+    gold = _load_golden(fixture)
     model = fill_state_by_name(_build('cuda', cr, cr_t)).cuda().train()
     model.model_t.eval()
     model.model_s.dropout.p = 0.0
-    seed = int(gold['seed']) if 'seed' in gold.files else 77
+    seed = int(gold['seed']) if 'seed' in gold else 77
     b = synth_kd_batch(n_vox, 2, seed=seed, image_hw=(64, 112)) if batch_of is None else batch_of(seed)
     s, t = b['student'], b['teacher']
     pc, ms = _kd_tensors(b, 'cuda')

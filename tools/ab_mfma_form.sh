@@ -8,7 +8,7 @@ bash tools/build_variant.sh _k32 "-DU2MKD_MFMA_GFX950_K32=1" conv_tp.hip conv_px
 for rep in 1 2; do
   for suf in "" _k32; do
     U2MKD_LIB_SUFFIX=$suf U2MKD_BENCH_WIDE=1 python bench.py --kernel-only > $OUT/ko${suf}_$rep.json 2> /dev/null
-    U2MKD_LIB_SUFFIX=$suf python bench.py --no-secondary --no-cpu-baseline --no-roofline --steps 30 --warmup 6 > $OUT/kd${suf}_$rep.json 2> /dev/null
+    U2MKD_LIB_SUFFIX=$suf python bench.py --full --no-secondary --no-cpu-baseline --no-roofline --steps 30 --warmup 6 > $OUT/kd${suf}_$rep.json 2> /dev/null
   done
 done
 for suf in "" _k32; do
