@@ -175,6 +175,8 @@ class _BatchNorm2dFunction(torch.autograd.Function):
                    bn.momentum if track else 0.0, int(relu), L.ptr(bn.running_mean if track else None),
                    L.ptr(bn.running_var if track else None), L.ptr(bn.num_batches_tracked if track else None),
                    L.ptr(ws), L.ptr(mean), L.ptr(invstd), L.ptr(y), st)
+            if track:       # (written through raw pointers: versions bumped as torch's in-place updates would)
+                torch._C._increment_version([t for t in (bn.running_mean, bn.running_var, bn.num_batches_tracked) if t is not None])
         else:
             mean, invstd = bn.running_mean, torch.rsqrt(bn.running_var + bn.eps)
             L.call('u2mkd_bn2d_eval_forward', L.ptr(x), L.ptr(res), b, c, hw, L.ptr(weight), L.ptr(bias), bn.eps, int(relu),
@@ -248,6 +250,8 @@ class _SyncBatchNorm2dFunction(torch.autograd.Function):
         L.call('u2mkd_bn_merge_stats_counted', L.ptr(gathered), world, c, float(bn.eps), float(bn.momentum if track else 0.0),
                L.ptr(bn.running_mean if track else None), L.ptr(bn.running_var if track else None), L.ptr(mean),
                L.ptr(invstd), L.ptr(total), L.ptr(bn.num_batches_tracked if track else None), L.stream())
+        if track:
+            torch._C._increment_version([t for t in (bn.running_mean, bn.running_var, bn.num_batches_tracked) if t is not None])
         y = torch.empty_like(x)
         L.call('u2mkd_bn2d_apply', L.ptr(x), L.ptr(res), b, c, hw, L.ptr(mean), L.ptr(invstd), L.ptr(weight), L.ptr(bias),
                int(relu), L.ptr(y), L.stream())

@@ -58,6 +58,9 @@ struct BatchNormRows : public torch::autograd::Function<BatchNormRows> {
                                              mf(running_mean), mf(running_var), cnt, relu, partial.data_ptr<float>(),
                                              mean.data_ptr<float>(), invstd.data_ptr<float>(), y.data_ptr<float>(), cur_stream()),
                   "u2mkd_bn_train_forward_res");
+            // written in place through raw pointers: versions bumped as torch's in-place updates would (eval_bn_affine's cache key)
+            for (const OptTensor *t : {&running_mean, &running_var, &counter})
+                if (t->has_value() && (*t)->defined()) torch::autograd::impl::bump_version(**t);
         } else {
             TORCH_CHECK(running_mean.has_value() && running_mean->defined(), "batch_norm_rows: eval mode needs running statistics");
             mean = *running_mean;

@@ -142,9 +142,17 @@ class FusedSGD(torch.optim.SGD):
             for _, fg, _ in plans:
                 self._adopt_state(fg)
             self._adopt = False
+        written = []
         for group, fg, grads in plans:
             with torch.cuda.device(fg.device):          # (the launch goes to the current stream of the GROUP's device)
                 self._launch(group, fg, grads)
+            written += [p for p, g in zip(fg.params, grads) if g is not None]
+            if group['momentum'] != 0:
+                written.append(fg.flat)                 # (the momentum buffers are views of it: one counter for all)
+        # torch's rule for in-place writes: the kernel wrote these through raw pointers, so their versions move as torch's
+        # SGD moves them -- caches keyed by version (functional.eval_bn_affine) miss, autograd's saved-tensor check holds.
+        # Before the global post hook re-stamps the weights' fragment images (functional.refresh_weight_fragments).
+        torch._C._increment_version(written)
         return loss
 
     def _launch(self, group, fg, grads):

@@ -1059,9 +1059,10 @@ def conv_eval_affine(input: SparseTensor, conv, scale, shift, relu, residual=Non
 
 def eval_bn_affine(bn):
     """(scale, shift) of an eval-mode BatchNorm as fp32 device vectors, cached on the module until a parameter, a running
-    statistic or eps changes (versions of the five tensors)."""
+    statistic or eps changes (versions of the four tensors -- every in-place writer of the library bumps them -- and the
+    epoch of ``invalidate_weight_caches`` for writes through ``.data``)."""
     key = (bn.running_mean._version, bn.running_var._version, None if bn.weight is None else bn.weight._version,
-           None if bn.bias is None else bn.bias._version, bn.eps, bn.running_mean.data_ptr())
+           None if bn.bias is None else bn.bias._version, bn.eps, bn.running_mean.data_ptr(), _WEIGHT_EPOCH[1])
     hit = bn.__dict__.get('_u2mkd_affine')
     if hit is not None and hit[0] == key:
         return hit[1], hit[2]
@@ -1074,15 +1075,20 @@ def eval_bn_affine(bn):
     return scale, shift
 
 
-_WEIGHT_EPOCH = [0]
+# [step epoch, invalidation epoch]: the first moves after every optimizer step and stamps trainable weights only (a frozen
+# weight's caches outlive the steps of the model trained next to it); the second moves only in invalidate_weight_caches
+_WEIGHT_EPOCH = [0, 0]
 
 
 def invalidate_weight_caches(*_):
-    """Forget every cached weight re-layout.  The caches are stamped with the tensor's in-place version counter and
-    storage address, which writes through ``.data`` (``p.data.add_`` of an EMA or a hand-written optimizer,
-    ``kernel.data.uniform_`` of a re-initialisation) do not move; so the stamp also carries this epoch, bumped after
-    EVERY ``torch.optim.Optimizer.step`` (global post hook below) and by whoever writes weights behind autograd's back."""
+    """Forget every cached weight re-layout and folded eval BatchNorm affine (``eval_bn_affine``).  The caches are stamped
+    with the tensor's in-place version counter and storage address, which writes through ``.data`` (``p.data.add_`` of an
+    EMA or a hand-written optimizer, ``kernel.data.uniform_`` of a re-initialisation, ``p.data.copy_`` of a re-load) do not
+    move; so the stamp also carries this call's epoch -- frozen weights included -- and, for trainable weights, the step
+    epoch bumped after EVERY ``torch.optim.Optimizer.step`` (global post hook below).  Whoever writes weights or BatchNorm
+    statistics behind autograd's back calls this."""
     _WEIGHT_EPOCH[0] += 1
+    _WEIGHT_EPOCH[1] += 1
 
 
 # Trainable weights whose MFMA-fragment images are live: (id(weight), slot) -> [weakref, slot, both, k, r, c, planes, data_ptr].
@@ -1133,9 +1139,9 @@ def refresh_weight_fragments(*_):
         _FRAG_TABLE[1] = first
         _FRAG_TABLE[2:] = [stage]          # alive until the next rebuild: the copy reads it asynchronously
     L.call('u2mkd_weight_fragments_batch', L.ptr(_FRAG_TABLE[0]), len(live), _FRAG_TABLE[1], L.stream())
-    epoch = _WEIGHT_EPOCH[0]
+    epoch = tuple(_WEIGHT_EPOCH)
     for w, job in live:
-        w.__dict__[job[1]] = ((w._version, job[7], epoch), job[2])
+        w.__dict__[job[1]] = ((w._version, job[7]) + epoch, job[2])
 
 
 try:
@@ -1155,15 +1161,15 @@ def _weight_layout(weight, transpose, fragments, arith=0):
     transpose: B_k[col][red] = weight[k][red][col] (else weight[k][col][red], the tensor as it is).
     fragments: MFMA operand-fragment order (u2mkd_weight_fragments) instead of row-major [K, ncol, nred].
     Fragments of BOTH orientations come from one launch (latency-bound: 5 us for one or for two) and are cached
-    on the tensor with its in-place version, storage address and (trainable weights) the optimizer-step epoch of
-    ``invalidate_weight_caches``, so the forward's launch also serves the input gradient of the same step but never a
+    on the tensor with its in-place version, storage address, the epoch of ``invalidate_weight_caches`` and (trainable
+    weights) the optimizer-step epoch, so the forward's launch also serves the input gradient of the same step but never a
     later step; row-major layouts are cached for FROZEN weights only (requires_grad False: the KD teacher, inference),
     trained weights are re-laid out per call."""
     if not transpose and not fragments:
         return weight
     k, r, c = weight.shape if weight.dim() == 3 else (1,) + tuple(weight.shape)     # 2-D: nn.Linear's [out, in], one offset
     frozen = not weight.requires_grad
-    stamp = (weight._version, weight.data_ptr(), _WEIGHT_EPOCH[0] if not frozen else -1)
+    stamp = (weight._version, weight.data_ptr(), _WEIGHT_EPOCH[0] if not frozen else -1, _WEIGHT_EPOCH[1])
     # the cache lives on the parameter: a reshaping view of it made per call (`conv.weight.squeeze(-1)` of a k = 1 Conv1d,
     # `.view(cout, cin)` of a 1x1 Conv2d) is a new tensor object every time and would re-lay the weight on every use
     holder, tag = weight, ''
@@ -1860,16 +1866,25 @@ def batch_norm(x: torch.Tensor, bn: torch.nn.modules.batchnorm._BatchNorm, relu:
     rv = bn.running_var if (not training or bn.track_running_stats) else None
     if residual is not None and not relu:
         raise ValueError('batch_norm: a residual input is fused together with the ReLU only')
+    # the kernels below write the running statistics and the step counter through raw pointers: their versions are bumped
+    # here, as torch's in-place updates would (functional.eval_bn_affine caches under them); the C++ path bumps its own
+    written = [t for t in (rm, rv, counter) if t is not None] if training else []
     if sync is not None:
-        return SyncBatchNormFunction.apply(x, bn.weight, bn.bias, rm, rv, factor, bn.eps, relu, sync[0], sync[1], residual, counter)
+        y = SyncBatchNormFunction.apply(x, bn.weight, bn.bias, rm, rv, factor, bn.eps, relu, sync[0], sync[1], residual, counter)
+        torch._C._increment_version(written)
+        return y
     if training and x.shape[0] < 2:
         raise ValueError(f'Expected more than 1 value per channel when training, got input size {tuple(x.shape)}')
     if stats is not None and training and stats.describes(x) and not bf16_rows() and (residual is None or residual.dtype == torch.float32):
         # the slab statistics came with x (the producing convolution's store): merge + apply, no statistics pass
-        return BatchNormFunction.apply(x, bn.weight, bn.bias, rm, rv, training, factor, bn.eps, relu, counter, residual, stats)
+        y = BatchNormFunction.apply(x, bn.weight, bn.bias, rm, rv, training, factor, bn.eps, relu, counter, residual, stats)
+        torch._C._increment_version(written)
+        return y
     h = _HOST if _HOST is not False else host_ops()
     if h is not None and x.dtype == torch.float32 and x.is_cuda and x.shape[0] > 0 and not bf16_rows() \
             and (residual is None or residual.dtype == torch.float32):
         # the same pass with its host side in C++ (csrc_host/host_ops.cpp: BatchNormRows)
         return h.batch_norm_rows(x, bn.weight, bn.bias, rm, rv, training, factor, bn.eps, relu, counter, residual)
-    return BatchNormFunction.apply(x, bn.weight, bn.bias, rm, rv, training, factor, bn.eps, relu, counter, residual)
+    y = BatchNormFunction.apply(x, bn.weight, bn.bias, rm, rv, training, factor, bn.eps, relu, counter, residual)
+    torch._C._increment_version(written)
+    return y
