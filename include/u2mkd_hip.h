@@ -547,121 +547,63 @@ int u2mkd_l2c_finish(const int32_t *order_d, const int32_t *seg_d, const int32_t
  * running = (1 - momentum) * running + momentum * batch.  Deterministic (slab partials in
  * `partial`, [u2mkd_bn_num_slabs(n), 2, c] floats, merged in slab order).
  * gamma / beta / running_* may be NULL.  relu != 0 fuses max(., 0) (backward re-derives the
- * mask from x).                                                                          */
+ * mask from x).  One entry per pass; what varies between the layers is an argument:
+ *   bf16_rows            the dtype of the ROWS x, res, y, dy, dx, dres [n, c]: 0 = fp32, != 0 = bf16 (BASELINE.json configs[4];
+ *                        under autocast the reference's nn.BatchNorm1d takes and returns half rows while its statistics stay
+ *                        fp32).  gamma, beta, running statistics, mean [c], invstd [c], partial, dgamma [c], dbeta [c], stats
+ *                        and sums are fp32 either way; a bf16 value is rounded once, at its store, and the backward recomputes
+ *                        the ReLU mask from the bf16 x with the forward's fp32 expression, so the two passes agree on it.
+ *   res / dres           may be NULL.  The tail of a ResidualBlock (core/models/build_blocks.py:80-83: relu(net(x) +
+ *                        downsample(x))) inside the BatchNorm passes: y = relu(bn(x) + res) forward; the backward masks dy with
+ *                        (bn(x) + res > 0), returns it as dres (the gradient of the residual branch) and continues with the
+ *                        BatchNorm gradients -- one read of res instead of an add kernel, a ReLU kernel and their two backward
+ *                        kernels.  relu must be set; u2mkd_bn_backward takes res and dres together or neither.
+ *   num_batches_tracked  may be NULL.  nn.BatchNorm's step counter (device int64): += 1 inside the statistics / merge launch
+ *                        instead of a one-element launch of its own per layer and step (torch.nn.SyncBatchNorm bumps it with an
+ *                        add_ of its own, torch/nn/modules/batchnorm.py).
+ *   keep                 may be NULL.  A second copy [2c] of the local sums of u2mkd_bn_backward_local: `sums` goes into the
+ *                        caller's all_reduce in place, `keep` stays this rank's (the parameter gradients, which DDP averages)
+ *                        -- replaces the copy between the two.                                                              */
 int64_t u2mkd_bn_num_slabs(int64_t n);
-int u2mkd_bn_train_forward(const float *x /*[n,c]*/, int64_t n, int32_t c, const float *gamma, const float *beta,
-                           float eps, float momentum, float *running_mean, float *running_var, int32_t relu,
-                           float *partial, float *mean /*[c] out*/, float *invstd /*[c] out*/, float *y /*[n,c]*/,
-                           u2mkd_stream_t s);
-/* the same with nn.BatchNorm's step counter: *num_batches_tracked (device int64, may be NULL) += 1 in the
- * statistics kernel instead of a one-element launch of its own per layer and step                        */
+int u2mkd_bn_train_forward(const void *x, const void *res, int32_t bf16_rows, int64_t n, int32_t c, const float *gamma,
+                           const float *beta, float eps, float momentum, float *running_mean, float *running_var,
+                           int64_t *num_batches_tracked, int32_t relu, float *partial, float *mean /*[c] out*/,
+                           float *invstd /*[c] out*/, void *y, u2mkd_stream_t s);
 /* Train-mode forward FROM slab partials computed elsewhere: `partial` [ceil(n / slab_rows)][2][c] = per slab of slab_rows
  * consecutive rows the per-channel (mean, centred second moment), as u2mkd_pairs_gather_sum_stats writes them in the producing
  * convolution's store.  Merge (running statistics, step counter) + normalise (+ residual, + ReLU): the statistics pass of
- * u2mkd_bn_train_forward_res is not run.  fp32 rows.                                                                        */
+ * u2mkd_bn_train_forward is not run.  fp32 rows.                                                                            */
 int u2mkd_bn_train_forward_from_partial(const float *x, const float *res, int64_t n, int32_t c, const float *gamma,
                                         const float *beta, float eps, float momentum, float *running_mean, float *running_var,
                                         int64_t *num_batches_tracked, int32_t relu, const float *partial, int32_t slab_rows,
                                         float *mean /*[c] out*/, float *invstd /*[c] out*/, float *y, u2mkd_stream_t s);
-int u2mkd_bn_train_forward_counted(const float *x /*[n,c]*/, int64_t n, int32_t c, const float *gamma, const float *beta,
-                                   float eps, float momentum, float *running_mean, float *running_var,
-                                   int64_t *num_batches_tracked, int32_t relu, float *partial, float *mean /*[c] out*/,
-                                   float *invstd /*[c] out*/, float *y /*[n,c]*/, u2mkd_stream_t s);
-int u2mkd_bn_eval_forward(const float *x, int64_t n, int32_t c, const float *gamma, const float *beta, float eps,
-                          const float *running_mean, const float *running_var, int32_t relu, float *invstd /*[c] out*/,
-                          float *y, u2mkd_stream_t s);
-/* The tail of a ResidualBlock (core/models/build_blocks.py:80-83: relu(net(x) + downsample(x))) in the BatchNorm
- * passes: y = relu(bn(x) + res) forward; backward masks dy with (bn(x) + res > 0), returns it as dres (the gradient
- * of the residual branch) and continues with the BatchNorm gradients -- one read of res instead of an add kernel,
- * a ReLU kernel and their two backward kernels.  res / dres [n, c]; relu must be set.                         */
-int u2mkd_bn_train_forward_res(const float *x, const float *res, int64_t n, int32_t c, const float *gamma, const float *beta,
-                               float eps, float momentum, float *running_mean, float *running_var,
-                               int64_t *num_batches_tracked, int32_t relu, float *partial, float *mean, float *invstd,
-                               float *y, u2mkd_stream_t s);
-int u2mkd_bn_eval_forward_res(const float *x, const float *res, int64_t n, int32_t c, const float *gamma, const float *beta,
-                              float eps, const float *running_mean, const float *running_var, int32_t relu,
-                              float *invstd /*[c] out*/, float *y, u2mkd_stream_t s);
-int u2mkd_bn_backward_res(const float *dy, const float *x, const float *res, int64_t n, int32_t c, const float *mean,
-                          const float *invstd, const float *gamma, const float *beta, int32_t relu, int32_t training,
-                          float *partial, float *dgamma, float *dbeta, float *dx, float *dres, u2mkd_stream_t s);
-int u2mkd_bn_backward(const float *dy, const float *x, int64_t n, int32_t c, const float *mean, const float *invstd,
-                      const float *gamma, const float *beta, int32_t relu, int32_t training, float *partial,
-                      float *dgamma /*[c]*/, float *dbeta /*[c]*/, float *dx /*[n,c]*/, u2mkd_stream_t s);
+int u2mkd_bn_eval_forward(const void *x, const void *res, int32_t bf16_rows, int64_t n, int32_t c, const float *gamma,
+                          const float *beta, float eps, const float *running_mean, const float *running_var, int32_t relu,
+                          float *invstd /*[c] out*/, void *y, u2mkd_stream_t s);
+int u2mkd_bn_backward(const void *dy, const void *x, const void *res, int32_t bf16_rows, int64_t n, int32_t c,
+                      const float *mean, const float *invstd, const float *gamma, const float *beta, int32_t relu,
+                      int32_t training, float *partial, float *dgamma /*[c]*/, float *dbeta /*[c]*/, void *dx, void *dres,
+                      u2mkd_stream_t s);
 
 /* SyncBatchNorm (utils.py:138-220, train_spformer.py:79) in pieces, so the caller can put ONE small
  * collective between them: local (mean, M2, count) -> all_gather -> merge in rank order (Chan) ->
- * normalise(+ReLU); backward: local (sum dy', sum dy'*xhat) -> all_reduce -> apply with the global
+ * normalise(+ residual, ReLU); backward: local (sum dy', sum dy'*xhat) -> all_reduce -> apply with the global
  * count.  stats rows are [2c+1] = mean[c], M2[c], count.                                        */
-int u2mkd_bn_local_stats(const float *x, int64_t n, int32_t c, float *partial /*[slabs,2,c]*/, float *stats /*[2c+1]*/,
-                         u2mkd_stream_t s);
+int u2mkd_bn_local_stats(const void *x, int32_t bf16_rows, int64_t n, int32_t c, float *partial /*[slabs,2,c]*/,
+                         float *stats /*[2c+1]*/, u2mkd_stream_t s);
 int u2mkd_bn_merge_stats(const float *gathered /*[world,2c+1]*/, int32_t world, int32_t c, float eps, float momentum,
                          float *running_mean, float *running_var, float *mean /*[c]*/, float *invstd /*[c]*/,
-                         float *total /*[1]*/, u2mkd_stream_t s);
-int u2mkd_bn_apply(const float *x, int64_t n, int32_t c, const float *mean, const float *invstd, const float *gamma,
-                   const float *beta, int32_t relu, float *y, u2mkd_stream_t s);
-int u2mkd_bn_backward_local(const float *dy, const float *x, int64_t n, int32_t c, const float *mean,
-                            const float *invstd, const float *gamma, const float *beta, int32_t relu,
-                            float *partial /*[slabs,2,c]*/, float *sums /*[2c]: dbeta, dgamma*/, u2mkd_stream_t s);
-int u2mkd_bn_backward_apply(const float *dy, const float *x, int64_t n, int32_t c, const float *total_n /*[1] device*/,
-                            const float *mean, const float *invstd, const float *gamma, const float *beta,
-                            int32_t relu, const float *sums /*[2c] over all ranks*/, float *dx, u2mkd_stream_t s);
-
-/* the same three pieces with the residual branch of a ResidualBlock (build_blocks.py:80-83 under SyncBatchNorm):
- * y = relu(bn(x) + res) in the apply pass; the backward recomputes the mask from x and res, dres = the masked dy */
-int u2mkd_bn_apply_res(const float *x, const float *res, int64_t n, int32_t c, const float *mean, const float *invstd,
-                       const float *gamma, const float *beta, int32_t relu, float *y, u2mkd_stream_t s);
-int u2mkd_bn_backward_local_res(const float *dy, const float *x, const float *res, int64_t n, int32_t c, const float *mean,
-                                const float *invstd, const float *gamma, const float *beta, int32_t relu, float *partial,
-                                float *sums, u2mkd_stream_t s);
-int u2mkd_bn_backward_apply_res(const float *dy, const float *x, const float *res, int64_t n, int32_t c, const float *total_n,
-                                const float *mean, const float *invstd, const float *gamma, const float *beta, int32_t relu,
-                                const float *sums, float *dx, float *dres, u2mkd_stream_t s);
-int u2mkd_bn_apply_res_bf16(const void *x, const void *res, int64_t n, int32_t c, const float *mean, const float *invstd,
-                            const float *gamma, const float *beta, int32_t relu, void *y, u2mkd_stream_t s);
-int u2mkd_bn_backward_local_res_bf16(const void *dy, const void *x, const void *res, int64_t n, int32_t c, const float *mean,
-                                     const float *invstd, const float *gamma, const float *beta, int32_t relu, float *partial,
-                                     float *sums, u2mkd_stream_t s);
-int u2mkd_bn_backward_apply_res_bf16(const void *dy, const void *x, const void *res, int64_t n, int32_t c, const float *total_n,
-                                     const float *mean, const float *invstd, const float *gamma, const float *beta,
-                                     int32_t relu, const float *sums, void *dx, void *dres, u2mkd_stream_t s);
-
-/* Two launches fewer per synchronising BatchNorm and pass (113 such layers per KD step at N > 1):
- * u2mkd_bn_merge_stats_counted = u2mkd_bn_merge_stats + nn.BatchNorm's `num_batches_tracked += 1` (int64 device scalar, may be
- * NULL) in the same launch (torch.nn.SyncBatchNorm bumps it with an add_ of its own, torch/nn/modules/batchnorm.py);
- * u2mkd_bn_backward_local_keep = u2mkd_bn_backward_local(_res)(_bf16) writing the local sums TWICE: `sums` [2c] goes into the
- * all_reduce in place, `keep` [2c] stays this rank's (the parameter gradients, which DDP averages) -- replaces the copy
- * between the two.  bf16_rows != 0: dy, x, res are bf16 rows; res may be NULL (no residual branch). */
-int u2mkd_bn_merge_stats_counted(const float *gathered /*[world,2c+1]*/, int32_t world, int32_t c, float eps, float momentum,
-                                 float *running_mean, float *running_var, float *mean, float *invstd, float *total,
-                                 int64_t *num_batches_tracked, u2mkd_stream_t s);
-int u2mkd_bn_backward_local_keep(const void *dy, const void *x, const void *res, int32_t bf16_rows, int64_t n, int32_t c,
-                                 const float *mean, const float *invstd, const float *gamma, const float *beta, int32_t relu,
-                                 float *partial, float *sums /*[2c]*/, float *keep /*[2c]*/, u2mkd_stream_t s);
-
-/* The BatchNorm entries above on BF16 ROWS (BASELINE.json configs[4]; under autocast the reference's nn.BatchNorm1d takes
- * and returns half rows while its statistics stay fp32): x, res, y, dy, dx, dres are bf16 [n, c]; gamma, beta, running
- * statistics, mean, invstd, partial, dgamma, dbeta, stats and sums are fp32 exactly as above; every value is rounded to
- * bf16 once, at its store.  The fused ReLU mask is recomputed in the backward from the bf16 x with the forward's fp32
- * expression, so forward and backward agree on it.                                                                  */
-int u2mkd_bn_train_forward_res_bf16(const void *x, const void *res, int64_t n, int32_t c, const float *gamma,
-                                    const float *beta, float eps, float momentum, float *running_mean, float *running_var,
-                                    int64_t *num_batches_tracked, int32_t relu, float *partial, float *mean, float *invstd,
-                                    void *y, u2mkd_stream_t s);
-int u2mkd_bn_eval_forward_res_bf16(const void *x, const void *res, int64_t n, int32_t c, const float *gamma, const float *beta,
-                                   float eps, const float *running_mean, const float *running_var, int32_t relu,
-                                   float *invstd, void *y, u2mkd_stream_t s);
-int u2mkd_bn_backward_res_bf16(const void *dy, const void *x, const void *res, int64_t n, int32_t c, const float *mean,
-                               const float *invstd, const float *gamma, const float *beta, int32_t relu, int32_t training,
-                               float *partial, float *dgamma, float *dbeta, void *dx, void *dres, u2mkd_stream_t s);
-int u2mkd_bn_local_stats_bf16(const void *x, int64_t n, int32_t c, float *partial, float *stats, u2mkd_stream_t s);
-int u2mkd_bn_apply_bf16(const void *x, int64_t n, int32_t c, const float *mean, const float *invstd, const float *gamma,
-                        const float *beta, int32_t relu, void *y, u2mkd_stream_t s);
-int u2mkd_bn_backward_local_bf16(const void *dy, const void *x, int64_t n, int32_t c, const float *mean, const float *invstd,
-                                 const float *gamma, const float *beta, int32_t relu, float *partial, float *sums,
-                                 u2mkd_stream_t s);
-int u2mkd_bn_backward_apply_bf16(const void *dy, const void *x, int64_t n, int32_t c, const float *total_n, const float *mean,
-                                 const float *invstd, const float *gamma, const float *beta, int32_t relu, const float *sums,
-                                 void *dx, u2mkd_stream_t s);
+                         float *total /*[1]*/, int64_t *num_batches_tracked, u2mkd_stream_t s);
+int u2mkd_bn_apply(const void *x, const void *res, int32_t bf16_rows, int64_t n, int32_t c, const float *mean,
+                   const float *invstd, const float *gamma, const float *beta, int32_t relu, void *y, u2mkd_stream_t s);
+int u2mkd_bn_backward_local(const void *dy, const void *x, const void *res, int32_t bf16_rows, int64_t n, int32_t c,
+                            const float *mean, const float *invstd, const float *gamma, const float *beta, int32_t relu,
+                            float *partial /*[slabs,2,c]*/, float *sums /*[2c]: dbeta, dgamma*/, float *keep /*[2c]*/,
+                            u2mkd_stream_t s);
+int u2mkd_bn_backward_apply(const void *dy, const void *x, const void *res, int32_t bf16_rows, int64_t n, int32_t c,
+                            const float *total_n /*[1] device*/, const float *mean, const float *invstd, const float *gamma,
+                            const float *beta, int32_t relu, const float *sums /*[2c] over all ranks*/, void *dx, void *dres,
+                            u2mkd_stream_t s);
 
 /* ---- SphereFormer / sptr window attention ---------------------------------------
  * replaces the extern "C" launchers of third_party/SparseTransformer/src/sptr:
@@ -838,11 +780,8 @@ int u2mkd_bn2d_apply(const float *x, const float *res, int64_t b, int32_t c, int
                      const float *invstd, const float *gamma, const float *beta, int32_t relu, float *y, u2mkd_stream_t s);
 int u2mkd_bn2d_backward_local(const float *dy, const float *x, const float *res, int64_t b, int32_t c, int64_t hw,
                               const float *mean, const float *invstd, const float *gamma, const float *beta, int32_t relu,
-                              void *workspace, float *sums /*[2c]*/, u2mkd_stream_t s);
-/* u2mkd_bn2d_backward_local with a second copy `keep` [2c] of the sums (as u2mkd_bn_backward_local_keep) */
-int u2mkd_bn2d_backward_local_keep(const float *dy, const float *x, const float *res, int64_t b, int32_t c, int64_t hw,
-                                   const float *mean, const float *invstd, const float *gamma, const float *beta, int32_t relu,
-                                   void *workspace, float *sums /*[2c]*/, float *keep /*[2c]*/, u2mkd_stream_t s);
+                              void *workspace, float *sums /*[2c]*/, float *keep /*[2c], may be NULL: as u2mkd_bn_backward_local*/,
+                              u2mkd_stream_t s);
 int u2mkd_bn2d_backward_apply(const float *dy, const float *x, const float *res, int64_t b, int32_t c, int64_t hw,
                               const float *total_n /*[1] device*/, const float *mean, const float *invstd, const float *gamma,
                               const float *beta, int32_t relu, const float *sums /*[2c] over all ranks*/, float *dx,

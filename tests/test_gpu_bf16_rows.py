@@ -214,8 +214,8 @@ def test_spvcnn_rows_travel_in_bf16_and_logits_stay_close_to_fp32(F, monkeypatch
     def spy(name, *a):
         if name.startswith('u2mkd_conv_forward_tiles') or name.startswith('u2mkd_conv_forward_pairs'):
             seen['conv_bf16' if name.endswith('_bf16') else 'conv_f32'] += 1
-        if name.startswith('u2mkd_bn_train_forward_res'):
-            seen['bn_bf16' if name.endswith('_bf16') else 'bn_f32'] += 1
+        if name == 'u2mkd_bn_train_forward':          # (x, res, bf16_rows, ...)
+            seen['bn_bf16' if a[2] else 'bn_f32'] += 1
         return real_call(name, *a)
     monkeypatch.setattr(F.L, 'call', spy)
     with _amp():

@@ -163,7 +163,8 @@ def test_sync_bn_pieces_emulate_two_ranks_on_one_gpu(hip, n0, n1, c, relu):
     """SyncBatchNorm at world_size 2, emulated on ONE GPU: a batch is cut into two UNEQUAL per-rank parts, every
     part goes through the per-rank pieces (u2mkd_bn_local_stats -> [all_gather = stacking the two [2C+1] rows] ->
     u2mkd_bn_merge_stats(world = 2) -> u2mkd_bn_apply;  u2mkd_bn_backward_local -> [all_reduce = the sum of the two
-    [2C] rows] -> u2mkd_bn_backward_apply) and the result must equal torch's BatchNorm1d over the whole batch in
+    [2C] rows] -> u2mkd_bn_backward_apply; fp32 rows, no residual, no step counter, no second copy of the sums: bf16_rows = 0
+    and res / dres / num_batches_tracked / keep = None) and the result must equal torch's BatchNorm1d over the whole batch in
     fp64: y, dx, the per-rank dgamma / dbeta (DDP averages them afterwards: their SUM is the full-batch gradient),
     the running statistics with the GLOBAL count (torch.nn.SyncBatchNorm semantics, core/models/utils.py:138-220)."""
     from u2mkd_amd import _lib as L
@@ -189,12 +190,12 @@ def test_sync_bn_pieces_emulate_two_ranks_on_one_gpu(hip, n0, n1, c, relu):
     for r, (xp, _) in enumerate(parts):
         n = xp.shape[0]
         partial = torch.empty(max(lib.u2mkd_bn_num_slabs(n), 1) * 2 * c, device='cuda')
-        L.call('u2mkd_bn_local_stats', L.ptr(xp), n, c, L.ptr(partial), L.ptr(stats[r]), st)
+        L.call('u2mkd_bn_local_stats', L.ptr(xp), 0, n, c, L.ptr(partial), L.ptr(stats[r]), st)
     assert stats[:, 2 * c].tolist() == [float(n0), float(n1)]
     run_mean, run_var = torch.zeros(c, device='cuda'), torch.ones(c, device='cuda')
     mean, invstd, total = torch.empty(c, device='cuda'), torch.empty(c, device='cuda'), torch.empty(1, device='cuda')
     L.call('u2mkd_bn_merge_stats', L.ptr(stats), 2, c, eps, mom, L.ptr(run_mean), L.ptr(run_var), L.ptr(mean), L.ptr(invstd),
-           L.ptr(total), st)
+           L.ptr(total), None, st)
     assert float(total) == n0 + n1
     assert float((run_mean.double() - ref.running_mean).abs().max()) < 1e-6
     assert float((run_var.double() - ref.running_var).abs().max()) < 1e-5
@@ -202,19 +203,20 @@ def test_sync_bn_pieces_emulate_two_ranks_on_one_gpu(hip, n0, n1, c, relu):
     for r, (xp, dyp) in enumerate(parts):
         n = xp.shape[0]
         y = torch.empty_like(xp)
-        L.call('u2mkd_bn_apply', L.ptr(xp), n, c, L.ptr(mean), L.ptr(invstd), L.ptr(gamma), L.ptr(beta), int(relu), L.ptr(y), st)
+        L.call('u2mkd_bn_apply', L.ptr(xp), None, 0, n, c, L.ptr(mean), L.ptr(invstd), L.ptr(gamma), L.ptr(beta), int(relu), L.ptr(y),
+               st)
         ys.append(y)
         partial = torch.empty(max(lib.u2mkd_bn_num_slabs(n), 1) * 2 * c, device='cuda')
-        L.call('u2mkd_bn_backward_local', L.ptr(dyp), L.ptr(xp), n, c, L.ptr(mean), L.ptr(invstd), L.ptr(gamma), L.ptr(beta),
-               int(relu), L.ptr(partial), L.ptr(sums[r]), st)
+        L.call('u2mkd_bn_backward_local', L.ptr(dyp), L.ptr(xp), None, 0, n, c, L.ptr(mean), L.ptr(invstd), L.ptr(gamma), L.ptr(beta),
+               int(relu), L.ptr(partial), L.ptr(sums[r]), None, st)
     assert float((torch.cat(ys).double() - yr).abs().max()) < 1e-5
     reduced = sums.sum(0).contiguous()                      # the all_reduce
     dxs = []
     for xp, dyp in parts:
         n = xp.shape[0]
         dx = torch.empty_like(xp)
-        L.call('u2mkd_bn_backward_apply', L.ptr(dyp), L.ptr(xp), n, c, L.ptr(total), L.ptr(mean), L.ptr(invstd), L.ptr(gamma),
-               L.ptr(beta), int(relu), L.ptr(reduced), L.ptr(dx), st)
+        L.call('u2mkd_bn_backward_apply', L.ptr(dyp), L.ptr(xp), None, 0, n, c, L.ptr(total), L.ptr(mean), L.ptr(invstd),
+               L.ptr(gamma), L.ptr(beta), int(relu), L.ptr(reduced), L.ptr(dx), None, st)
         dxs.append(dx)
     scale = max(1.0, float(xr.grad.abs().max()))
     assert float((torch.cat(dxs).double() - xr.grad).abs().max()) < 1e-4 * scale
@@ -222,6 +224,50 @@ def test_sync_bn_pieces_emulate_two_ranks_on_one_gpu(hip, n0, n1, c, relu):
     gs = max(1.0, float(ref.weight.grad.abs().max()))
     assert float((reduced[:c].double() - ref.bias.grad).abs().max()) < 1e-4 * gs
     assert float((reduced[c:].double() - ref.weight.grad).abs().max()) < 1e-4 * gs
+
+
+@pytest.mark.parametrize('n', [777, 5])             # several slabs with a ragged last one | fewer rows than one slab
+@pytest.mark.parametrize('with_res', [False, True])
+@pytest.mark.parametrize('bf16', [False, True])
+def test_row_bn_optional_arguments_change_nothing_else(hip, bf16, with_res, n):
+    """The arguments that one entry per pass made optional only ADD an output, bit for bit: u2mkd_bn_backward_local
+    writes the same `sums` with keep = None and with a `keep` buffer (which then equals `sums`); u2mkd_bn_merge_stats
+    writes the same mean / invstd / total / running statistics with num_batches_tracked = None and with a device
+    counter (which goes from 0 to 1).  fp32 and bf16 rows, with and without the residual branch (relu = 1)."""
+    from u2mkd_amd import _lib as L
+    c, eps, mom = 96, 1e-5, 0.1
+    torch.manual_seed(n + 2 * bf16 + with_res)
+    rows = torch.bfloat16 if bf16 else torch.float32
+    x = (torch.randn(n, c, device='cuda') * 1.7 + 0.6).to(rows)
+    dy = torch.randn(n, c, device='cuda').to(rows)
+    res = torch.randn(n, c, device='cuda').to(rows) if with_res else None
+    gamma = torch.rand(c, device='cuda') + 0.5
+    beta = torch.rand(c, device='cuda') - 0.5
+    lib, st = L.load(), L.stream()
+    slabs = lib.u2mkd_bn_num_slabs(n)
+    assert slabs > 1 if n == 777 else slabs == 1
+    partial = torch.empty(slabs * 2 * c, device='cuda')
+    nan = lambda k: torch.full((k,), float('nan'), device='cuda')          # an output nobody wrote compares unequal
+    stats = torch.empty(1, 2 * c + 1, device='cuda')
+    L.call('u2mkd_bn_local_stats', L.ptr(x), int(bf16), n, c, L.ptr(partial), L.ptr(stats), st)
+    merged = []
+    for counter in (None, torch.zeros((), dtype=torch.int64, device='cuda')):
+        out = [torch.zeros(c, device='cuda'), torch.ones(c, device='cuda')] + [nan(c), nan(c), nan(1)]
+        run_mean, run_var, mean, invstd, total = out
+        L.call('u2mkd_bn_merge_stats', L.ptr(stats), 1, c, eps, mom, L.ptr(run_mean), L.ptr(run_var), L.ptr(mean), L.ptr(invstd),
+               L.ptr(total), L.ptr(counter), st)
+        merged.append(out)
+    assert int(counter) == 1
+    for a, b in zip(*merged):
+        assert torch.equal(a, b)
+    assert float(total) == n and float(run_mean.abs().max()) > 0
+    both = []
+    for keep in (None, nan(2 * c)):
+        sums = nan(2 * c)
+        L.call('u2mkd_bn_backward_local', L.ptr(dy), L.ptr(x), L.ptr(res), int(bf16), n, c, L.ptr(mean), L.ptr(invstd), L.ptr(gamma),
+               L.ptr(beta), 1, L.ptr(partial), L.ptr(sums), L.ptr(keep), st)
+        both.append(sums)
+    assert torch.equal(both[0], both[1]) and torch.equal(keep, both[1])
 
 
 def test_teacher_only_step_masks_the_loss_to_key_frame_voxels(hip):

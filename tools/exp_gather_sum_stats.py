@@ -29,7 +29,7 @@ for stride, cout in ((2, 64), (2, 128), (4, 128), (4, 256), (8, 256), (16, 256),
     rm = torch.zeros(cout, device='cuda'); rv = torch.ones(cout, device='cuda')
     mean = torch.empty(cout, device='cuda'); inv = torch.empty(cout, device='cuda'); yy = torch.empty_like(out)
     p2 = torch.empty(max(int(lib.u2mkd_bn_num_slabs(n)), 1) * 2 * cout, device='cuda')
-    t_bn = ev(lambda: L.call('u2mkd_bn_train_forward_res', L.ptr(out), None, n, cout, L.ptr(g), L.ptr(bt), 1e-5, 0.1, L.ptr(rm), L.ptr(rv), None, 1,
+    t_bn = ev(lambda: L.call('u2mkd_bn_train_forward', L.ptr(out), None, 0, n, cout, L.ptr(g), L.ptr(bt), 1e-5, 0.1, L.ptr(rm), L.ptr(rv), None, 1,
                              L.ptr(p2), L.ptr(mean), L.ptr(inv), L.ptr(yy), st), 50)
     t_bnp = ev(lambda: L.call('u2mkd_bn_train_forward_from_partial', L.ptr(out), None, n, cout, L.ptr(g), L.ptr(bt), 1e-5, 0.1, L.ptr(rm), L.ptr(rv), None, 1,
                               L.ptr(partial), rows, L.ptr(mean), L.ptr(inv), L.ptr(yy), st), 50)

@@ -68,8 +68,7 @@ SIGNATURES = {
     'u2mkd_bn2d_backward': (C.c_int, [_p, _p, _p, _i64, _i32, _i64, _p, _p, _p, _p, _i32, _i32, _p, _p, _p, _p, _p, _p]),
     'u2mkd_bn2d_local_stats': (C.c_int, [_p, _i64, _i32, _i64, _p, _p, _p]),
     'u2mkd_bn2d_apply': (C.c_int, [_p, _p, _i64, _i32, _i64, _p, _p, _p, _p, _i32, _p, _p]),
-    'u2mkd_bn2d_backward_local': (C.c_int, [_p, _p, _p, _i64, _i32, _i64, _p, _p, _p, _p, _i32, _p, _p, _p]),
-    'u2mkd_bn2d_backward_local_keep': (C.c_int, [_p, _p, _p, _i64, _i32, _i64, _p, _p, _p, _p, _i32, _p, _p, _p, _p]),
+    'u2mkd_bn2d_backward_local': (C.c_int, [_p, _p, _p, _i64, _i32, _i64, _p, _p, _p, _p, _i32, _p, _p, _p, _p]),
     'u2mkd_bn2d_backward_apply': (C.c_int, [_p, _p, _p, _i64, _i32, _i64, _p, _p, _p, _p, _p, _i32, _p, _p, _p, _p]),
     'u2mkd_linear_forward_x3': (C.c_int, [_p, _i64, _i32, _p, _i32, _p, _p, _p]),
     'u2mkd_conv_pairs_f16x2_supported': (_i32, [_i32, _i32]),
@@ -94,34 +93,15 @@ SIGNATURES = {
     'u2mkd_convolution_forward': (C.c_int, [_p, _i64, _i32, _p, _i64, _i32, _p, _p, _p, _i32, _i32, _p, _sz, _p]),
     'u2mkd_convolution_backward': (C.c_int, [_p, _i64, _i32, _p, _p, _i64, _i32, _p, _p, _p, _p, _i32, _i32, _p, _sz, _p]),
     'u2mkd_bn_num_slabs': (_i64, [_i64]),
-    'u2mkd_bn_train_forward': (C.c_int, [_p, _i64, _i32, _p, _p, _f32, _f32, _p, _p, _i32, _p, _p, _p, _p, _p]),
-    'u2mkd_bn_train_forward_counted': (C.c_int, [_p, _i64, _i32, _p, _p, _f32, _f32, _p, _p, _p, _i32, _p, _p, _p, _p, _p]),
-    'u2mkd_bn_eval_forward': (C.c_int, [_p, _i64, _i32, _p, _p, _f32, _p, _p, _i32, _p, _p, _p]),
-    'u2mkd_bn_train_forward_res': (C.c_int, [_p, _p, _i64, _i32, _p, _p, _f32, _f32, _p, _p, _p, _i32, _p, _p, _p, _p, _p]),
+    'u2mkd_bn_train_forward': (C.c_int, [_p, _p, _i32, _i64, _i32, _p, _p, _f32, _f32, _p, _p, _p, _i32, _p, _p, _p, _p, _p]),
     'u2mkd_bn_train_forward_from_partial': (C.c_int, [_p, _p, _i64, _i32, _p, _p, _f32, _f32, _p, _p, _p, _i32, _p, _i32, _p, _p, _p, _p]),
-    'u2mkd_bn_eval_forward_res': (C.c_int, [_p, _p, _i64, _i32, _p, _p, _f32, _p, _p, _i32, _p, _p, _p]),
-    'u2mkd_bn_backward_res': (C.c_int, [_p, _p, _p, _i64, _i32, _p, _p, _p, _p, _i32, _i32, _p, _p, _p, _p, _p, _p]),
-    'u2mkd_bn_backward': (C.c_int, [_p, _p, _i64, _i32, _p, _p, _p, _p, _i32, _i32, _p, _p, _p, _p, _p]),
-    'u2mkd_bn_local_stats': (C.c_int, [_p, _i64, _i32, _p, _p, _p]),
-    'u2mkd_bn_merge_stats': (C.c_int, [_p, _i32, _i32, _f32, _f32, _p, _p, _p, _p, _p, _p]),
-    'u2mkd_bn_merge_stats_counted': (C.c_int, [_p, _i32, _i32, _f32, _f32, _p, _p, _p, _p, _p, _p, _p]),
-    'u2mkd_bn_backward_local_keep': (C.c_int, [_p, _p, _p, _i32, _i64, _i32, _p, _p, _p, _p, _i32, _p, _p, _p, _p]),
-    'u2mkd_bn_apply': (C.c_int, [_p, _i64, _i32, _p, _p, _p, _p, _i32, _p, _p]),
-    'u2mkd_bn_backward_local': (C.c_int, [_p, _p, _i64, _i32, _p, _p, _p, _p, _i32, _p, _p, _p]),
-    'u2mkd_bn_backward_apply': (C.c_int, [_p, _p, _i64, _i32, _p, _p, _p, _p, _p, _i32, _p, _p, _p]),
-    'u2mkd_bn_train_forward_res_bf16': (C.c_int, [_p, _p, _i64, _i32, _p, _p, _f32, _f32, _p, _p, _p, _i32, _p, _p, _p, _p, _p]),
-    'u2mkd_bn_eval_forward_res_bf16': (C.c_int, [_p, _p, _i64, _i32, _p, _p, _f32, _p, _p, _i32, _p, _p, _p]),
-    'u2mkd_bn_backward_res_bf16': (C.c_int, [_p, _p, _p, _i64, _i32, _p, _p, _p, _p, _i32, _i32, _p, _p, _p, _p, _p, _p]),
-    'u2mkd_bn_local_stats_bf16': (C.c_int, [_p, _i64, _i32, _p, _p, _p]),
-    'u2mkd_bn_apply_res': (C.c_int, [_p, _p, _i64, _i32, _p, _p, _p, _p, _i32, _p, _p]),
-    'u2mkd_bn_backward_local_res': (C.c_int, [_p, _p, _p, _i64, _i32, _p, _p, _p, _p, _i32, _p, _p, _p]),
-    'u2mkd_bn_backward_apply_res': (C.c_int, [_p, _p, _p, _i64, _i32, _p, _p, _p, _p, _p, _i32, _p, _p, _p, _p]),
-    'u2mkd_bn_apply_res_bf16': (C.c_int, [_p, _p, _i64, _i32, _p, _p, _p, _p, _i32, _p, _p]),
-    'u2mkd_bn_backward_local_res_bf16': (C.c_int, [_p, _p, _p, _i64, _i32, _p, _p, _p, _p, _i32, _p, _p, _p]),
-    'u2mkd_bn_backward_apply_res_bf16': (C.c_int, [_p, _p, _p, _i64, _i32, _p, _p, _p, _p, _p, _i32, _p, _p, _p, _p]),
-    'u2mkd_bn_apply_bf16': (C.c_int, [_p, _i64, _i32, _p, _p, _p, _p, _i32, _p, _p]),
-    'u2mkd_bn_backward_local_bf16': (C.c_int, [_p, _p, _i64, _i32, _p, _p, _p, _p, _i32, _p, _p, _p]),
-    'u2mkd_bn_backward_apply_bf16': (C.c_int, [_p, _p, _i64, _i32, _p, _p, _p, _p, _p, _i32, _p, _p, _p]),
+    'u2mkd_bn_eval_forward': (C.c_int, [_p, _p, _i32, _i64, _i32, _p, _p, _f32, _p, _p, _i32, _p, _p, _p]),
+    'u2mkd_bn_backward': (C.c_int, [_p, _p, _p, _i32, _i64, _i32, _p, _p, _p, _p, _i32, _i32, _p, _p, _p, _p, _p, _p]),
+    'u2mkd_bn_local_stats': (C.c_int, [_p, _i32, _i64, _i32, _p, _p, _p]),
+    'u2mkd_bn_merge_stats': (C.c_int, [_p, _i32, _i32, _f32, _f32, _p, _p, _p, _p, _p, _p, _p]),
+    'u2mkd_bn_apply': (C.c_int, [_p, _p, _i32, _i64, _i32, _p, _p, _p, _p, _i32, _p, _p]),
+    'u2mkd_bn_backward_local': (C.c_int, [_p, _p, _p, _i32, _i64, _i32, _p, _p, _p, _p, _i32, _p, _p, _p, _p]),
+    'u2mkd_bn_backward_apply': (C.c_int, [_p, _p, _p, _i32, _i64, _i32, _p, _p, _p, _p, _p, _i32, _p, _p, _p, _p]),
     'u2mkd_sptr_window_keys': (C.c_int, [_p, _p, _i64, _p, _p, _f32, _f32, _f32, _p, _p]),
     'u2mkd_select_mse_partials': (_i32, []),
     'u2mkd_select_mse_forward': (C.c_int, [_p, _p, _p, _i64, _i32, _p, _p, _p, _p]),

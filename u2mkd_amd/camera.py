@@ -247,7 +247,7 @@ class _SyncBatchNorm2dFunction(torch.autograd.Function):
         mean, invstd, total = mit[:c], mit[c:2 * c], mit[2 * c:]
         track = bn.running_mean is not None
         # (the step counter is bumped inside the merge launch)
-        L.call('u2mkd_bn_merge_stats_counted', L.ptr(gathered), world, c, float(bn.eps), float(bn.momentum if track else 0.0),
+        L.call('u2mkd_bn_merge_stats', L.ptr(gathered), world, c, float(bn.eps), float(bn.momentum if track else 0.0),
                L.ptr(bn.running_mean if track else None), L.ptr(bn.running_var if track else None), L.ptr(mean),
                L.ptr(invstd), L.ptr(total), L.ptr(bn.num_batches_tracked if track else None), L.stream())
         if track:
@@ -271,7 +271,7 @@ class _SyncBatchNorm2dFunction(torch.autograd.Function):
         ws = torch.empty(max(L.load().u2mkd_bn2d_workspace_bytes(b, c, hw), 16), dtype=torch.uint8, device=dev)
         both = torch.empty(2, 2 * c, dtype=torch.float32, device=dev)
         sums, local = both[0], both[1]            # `sums` into the all_reduce in place; `local` = this rank's parameter gradients (DDP averages them)
-        L.call('u2mkd_bn2d_backward_local_keep', L.ptr(dy), L.ptr(x), L.ptr(res), b, c, hw, L.ptr(mean), L.ptr(invstd),
+        L.call('u2mkd_bn2d_backward_local', L.ptr(dy), L.ptr(x), L.ptr(res), b, c, hw, L.ptr(mean), L.ptr(invstd),
                L.ptr(weight), L.ptr(bias), int(ctx.relu), L.ptr(ws), L.ptr(sums), L.ptr(local), L.stream())
         note_collective('all_reduce', sums)
         if ctx.world > 1:

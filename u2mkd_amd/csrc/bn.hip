@@ -581,8 +581,8 @@ static int bn_backward_impl(const T *dy, const T *x, const T *res, int64_t n, in
                             const float *invstd, const float *gamma, const float *beta, int32_t relu, int32_t training,
                             float *partial, float *dgamma, float *dbeta, T *dx, T *dres, u2mkd_stream_t s) {
     U2_REQUIRE(c > 0 && c % 4 == 0 && c <= 1024, "u2mkd_bn_backward: c=%d must be a multiple of 4 in 4..1024", c);
-    U2_REQUIRE((res == nullptr) == (dres == nullptr), "u2mkd_bn_backward_res: res and dres go together");
-    U2_REQUIRE(res == nullptr || relu, "u2mkd_bn_backward_res: a residual input is only fused with the ReLU form");
+    U2_REQUIRE((res == nullptr) == (dres == nullptr), "u2mkd_bn_backward: res and dres go together");
+    U2_REQUIRE(res == nullptr || relu, "u2mkd_bn_backward: a residual input is only fused with the ReLU form");
     if (n == 0) return 0;
     U2_REQUIRE(dy && x && mean && invstd && partial && dgamma && dbeta && dx, "u2mkd_bn_backward: null pointer");
     hipStream_t st = as_stream(s);
@@ -619,8 +619,8 @@ static int bn_local_stats_impl(const T *x, int64_t n, int32_t c, float *partial,
 }
 
 template <typename T>
-static int bn_apply_impl(const T *x, int64_t n, int32_t c, const float *mean, const float *invstd, const float *gamma,
-                         const float *beta, int32_t relu, T *y, u2mkd_stream_t s, const T *res = nullptr) {
+static int bn_apply_impl(const T *x, const T *res, int64_t n, int32_t c, const float *mean, const float *invstd,
+                         const float *gamma, const float *beta, int32_t relu, T *y, u2mkd_stream_t s) {
     U2_REQUIRE(c > 0 && c % 4 == 0, "u2mkd_bn_apply: c=%d must be a positive multiple of 4", c);
     if (n == 0) return 0;
     U2_REQUIRE(x && mean && invstd && y, "u2mkd_bn_apply: null pointer");
@@ -631,9 +631,9 @@ static int bn_apply_impl(const T *x, int64_t n, int32_t c, const float *mean, co
 }
 
 template <typename T>
-static int bn_backward_local_impl(const T *dy, const T *x, int64_t n, int32_t c, const float *mean, const float *invstd,
-                                  const float *gamma, const float *beta, int32_t relu, float *partial, float *sums,
-                                  u2mkd_stream_t s, const T *res = nullptr, float *keep = nullptr) {
+static int bn_backward_local_impl(const T *dy, const T *x, const T *res, int64_t n, int32_t c, const float *mean,
+                                  const float *invstd, const float *gamma, const float *beta, int32_t relu, float *partial,
+                                  float *sums, float *keep, u2mkd_stream_t s) {
     U2_REQUIRE(c > 0 && c % 4 == 0 && c <= 1024, "u2mkd_bn_backward_local: c=%d must be a multiple of 4 in 4..1024", c);
     U2_REQUIRE(sums, "u2mkd_bn_backward_local: null pointer");
     hipStream_t st = as_stream(s);
@@ -652,9 +652,9 @@ static int bn_backward_local_impl(const T *dy, const T *x, int64_t n, int32_t c,
 }
 
 template <typename T>
-static int bn_backward_apply_impl(const T *dy, const T *x, int64_t n, int32_t c, const float *total_n, const float *mean,
-                                  const float *invstd, const float *gamma, const float *beta, int32_t relu,
-                                  const float *sums, T *dx, u2mkd_stream_t s, const T *res = nullptr, T *dres = nullptr) {
+static int bn_backward_apply_impl(const T *dy, const T *x, const T *res, int64_t n, int32_t c, const float *total_n,
+                                  const float *mean, const float *invstd, const float *gamma, const float *beta, int32_t relu,
+                                  const float *sums, T *dx, T *dres, u2mkd_stream_t s) {
     U2_REQUIRE(c > 0 && c % 4 == 0, "u2mkd_bn_backward_apply: c=%d must be a positive multiple of 4", c);
     if (n == 0) return 0;
     U2_REQUIRE(dy && x && total_n && mean && invstd && sums && dx, "u2mkd_bn_backward_apply: null pointer");
@@ -668,19 +668,25 @@ static int bn_backward_apply_impl(const T *dy, const T *x, int64_t n, int32_t c,
 
 using namespace u2mkd;
 
+// the row pointers of the entries below as the rows of one dtype
 #define BF(p) reinterpret_cast<const bf16row *>(p)
 #define BFW(p) reinterpret_cast<bf16row *>(p)
+#define F32(p) reinterpret_cast<const float *>(p)
+#define F32W(p) reinterpret_cast<float *>(p)
 
 extern "C" {
 
 int64_t u2mkd_bn_num_slabs(int64_t n) { return n > 0 ? (n + kBnSlabRows - 1) / kBnSlabRows : 0; }
 
-int u2mkd_bn_train_forward_res(const float *x, const float *res, int64_t n, int32_t c, const float *gamma, const float *beta,
-                               float eps, float momentum, float *running_mean, float *running_var,
-                               int64_t *num_batches_tracked, int32_t relu, float *partial, float *mean, float *invstd, float *y,
-                               u2mkd_stream_t s) {
-    return bn_train_forward_impl<float>(x, res, n, c, gamma, beta, eps, momentum, running_mean, running_var,
-                                        num_batches_tracked, relu, partial, mean, invstd, y, s);
+int u2mkd_bn_train_forward(const void *x, const void *res, int32_t bf16_rows, int64_t n, int32_t c, const float *gamma,
+                           const float *beta, float eps, float momentum, float *running_mean, float *running_var,
+                           int64_t *num_batches_tracked, int32_t relu, float *partial, float *mean, float *invstd, void *y,
+                           u2mkd_stream_t s) {
+    if (bf16_rows)
+        return bn_train_forward_impl<bf16row>(BF(x), BF(res), n, c, gamma, beta, eps, momentum, running_mean, running_var,
+                                              num_batches_tracked, relu, partial, mean, invstd, BFW(y), s);
+    return bn_train_forward_impl<float>(F32(x), F32(res), n, c, gamma, beta, eps, momentum, running_mean, running_var,
+                                        num_batches_tracked, relu, partial, mean, invstd, F32W(y), s);
 }
 
 int u2mkd_bn_train_forward_from_partial(const float *x, const float *res, int64_t n, int32_t c, const float *gamma,
@@ -691,183 +697,67 @@ int u2mkd_bn_train_forward_from_partial(const float *x, const float *res, int64_
                                               num_batches_tracked, relu, partial, slab_rows, mean, invstd, y, s);
 }
 
-int u2mkd_bn_train_forward_counted(const float *x, int64_t n, int32_t c, const float *gamma, const float *beta, float eps,
-                                   float momentum, float *running_mean, float *running_var, int64_t *num_batches_tracked,
-                                   int32_t relu, float *partial /*[slabs,2,c]*/, float *mean /*[c]*/,
-                                   float *invstd /*[c]*/, float *y, u2mkd_stream_t s) {
-    return u2mkd_bn_train_forward_res(x, nullptr, n, c, gamma, beta, eps, momentum, running_mean, running_var,
-                                      num_batches_tracked, relu, partial, mean, invstd, y, s);
+int u2mkd_bn_eval_forward(const void *x, const void *res, int32_t bf16_rows, int64_t n, int32_t c, const float *gamma,
+                          const float *beta, float eps, const float *running_mean, const float *running_var, int32_t relu,
+                          float *invstd, void *y, u2mkd_stream_t s) {
+    if (bf16_rows)
+        return bn_eval_forward_impl<bf16row>(BF(x), BF(res), n, c, gamma, beta, eps, running_mean, running_var, relu, invstd,
+                                             BFW(y), s);
+    return bn_eval_forward_impl<float>(F32(x), F32(res), n, c, gamma, beta, eps, running_mean, running_var, relu, invstd,
+                                       F32W(y), s);
 }
 
-int u2mkd_bn_train_forward(const float *x, int64_t n, int32_t c, const float *gamma, const float *beta, float eps,
-                           float momentum, float *running_mean, float *running_var, int32_t relu,
-                           float *partial /*[slabs,2,c]*/, float *mean /*[c]*/, float *invstd /*[c]*/, float *y,
-                           u2mkd_stream_t s) {
-    return u2mkd_bn_train_forward_counted(x, n, c, gamma, beta, eps, momentum, running_mean, running_var, nullptr, relu,
-                                          partial, mean, invstd, y, s);
-}
-
-int u2mkd_bn_eval_forward_res(const float *x, const float *res, int64_t n, int32_t c, const float *gamma, const float *beta,
-                              float eps, const float *running_mean, const float *running_var, int32_t relu,
-                              float *invstd /*[c]*/, float *y, u2mkd_stream_t s) {
-    return bn_eval_forward_impl<float>(x, res, n, c, gamma, beta, eps, running_mean, running_var, relu, invstd, y, s);
-}
-
-int u2mkd_bn_eval_forward(const float *x, int64_t n, int32_t c, const float *gamma, const float *beta, float eps,
-                          const float *running_mean, const float *running_var, int32_t relu, float *invstd /*[c]*/,
-                          float *y, u2mkd_stream_t s) {
-    return u2mkd_bn_eval_forward_res(x, nullptr, n, c, gamma, beta, eps, running_mean, running_var, relu, invstd, y, s);
-}
-
-int u2mkd_bn_backward_res(const float *dy, const float *x, const float *res, int64_t n, int32_t c, const float *mean,
-                          const float *invstd, const float *gamma, const float *beta, int32_t relu, int32_t training,
-                          float *partial, float *dgamma, float *dbeta, float *dx, float *dres, u2mkd_stream_t s) {
-    return bn_backward_impl<float>(dy, x, res, n, c, mean, invstd, gamma, beta, relu, training, partial, dgamma, dbeta, dx,
-                                   dres, s);
-}
-
-int u2mkd_bn_backward(const float *dy, const float *x, int64_t n, int32_t c, const float *mean, const float *invstd,
-                      const float *gamma, const float *beta, int32_t relu, int32_t training, float *partial,
-                      float *dgamma /*[c]*/, float *dbeta /*[c]*/, float *dx, u2mkd_stream_t s) {
-    return u2mkd_bn_backward_res(dy, x, nullptr, n, c, mean, invstd, gamma, beta, relu, training, partial, dgamma, dbeta, dx,
-                                 nullptr, s);
+int u2mkd_bn_backward(const void *dy, const void *x, const void *res, int32_t bf16_rows, int64_t n, int32_t c,
+                      const float *mean, const float *invstd, const float *gamma, const float *beta, int32_t relu,
+                      int32_t training, float *partial, float *dgamma, float *dbeta, void *dx, void *dres, u2mkd_stream_t s) {
+    if (bf16_rows)
+        return bn_backward_impl<bf16row>(BF(dy), BF(x), BF(res), n, c, mean, invstd, gamma, beta, relu, training, partial,
+                                         dgamma, dbeta, BFW(dx), BFW(dres), s);
+    return bn_backward_impl<float>(F32(dy), F32(x), F32(res), n, c, mean, invstd, gamma, beta, relu, training, partial, dgamma,
+                                   dbeta, F32W(dx), F32W(dres), s);
 }
 
 /* ---- SyncBatchNorm pieces: local statistics | (all_gather by the caller) | merge | apply, and
  * local sums | (all_reduce by the caller) | apply in the backward ---- */
-int u2mkd_bn_local_stats(const float *x, int64_t n, int32_t c, float *partial, float *stats /*[2c+1]*/,
+int u2mkd_bn_local_stats(const void *x, int32_t bf16_rows, int64_t n, int32_t c, float *partial, float *stats,
                          u2mkd_stream_t s) {
-    return bn_local_stats_impl<float>(x, n, c, partial, stats, s);
+    if (bf16_rows) return bn_local_stats_impl<bf16row>(BF(x), n, c, partial, stats, s);
+    return bn_local_stats_impl<float>(F32(x), n, c, partial, stats, s);
 }
 
-int u2mkd_bn_merge_stats(const float *gathered /*[world,2c+1]*/, int32_t world, int32_t c, float eps, float momentum,
-                         float *running_mean, float *running_var, float *mean, float *invstd, float *total,
+int u2mkd_bn_merge_stats(const float *gathered, int32_t world, int32_t c, float eps, float momentum, float *running_mean,
+                         float *running_var, float *mean, float *invstd, float *total, int64_t *num_batches_tracked,
                          u2mkd_stream_t s) {
     U2_REQUIRE(gathered && mean && invstd && total && world > 0 && c > 0, "u2mkd_bn_merge_stats: bad arguments");
     hipLaunchKernelGGL(bn_sync_merge_kernel, dim3((unsigned)ceil_div(c, 64)), dim3(64), 0, as_stream(s), gathered, world, c,
-                       eps, momentum, running_mean, running_var, mean, invstd, total);
+                       eps, momentum, running_mean, running_var, mean, invstd, total, num_batches_tracked);
     return check_launch("u2mkd_bn_merge_stats");
 }
 
-/* the same merge, and num_batches_tracked += 1 (may be NULL) in the same launch */
-int u2mkd_bn_merge_stats_counted(const float *gathered, int32_t world, int32_t c, float eps, float momentum,
-                                 float *running_mean, float *running_var, float *mean, float *invstd, float *total,
-                                 int64_t *num_batches_tracked, u2mkd_stream_t s) {
-    U2_REQUIRE(gathered && mean && invstd && total && world > 0 && c > 0, "u2mkd_bn_merge_stats_counted: bad arguments");
-    hipLaunchKernelGGL(bn_sync_merge_kernel, dim3((unsigned)ceil_div(c, 64)), dim3(64), 0, as_stream(s), gathered, world, c,
-                       eps, momentum, running_mean, running_var, mean, invstd, total, num_batches_tracked);
-    return check_launch("u2mkd_bn_merge_stats_counted");
+int u2mkd_bn_apply(const void *x, const void *res, int32_t bf16_rows, int64_t n, int32_t c, const float *mean,
+                   const float *invstd, const float *gamma, const float *beta, int32_t relu, void *y, u2mkd_stream_t s) {
+    if (bf16_rows) return bn_apply_impl<bf16row>(BF(x), BF(res), n, c, mean, invstd, gamma, beta, relu, BFW(y), s);
+    return bn_apply_impl<float>(F32(x), F32(res), n, c, mean, invstd, gamma, beta, relu, F32W(y), s);
 }
 
-int u2mkd_bn_apply(const float *x, int64_t n, int32_t c, const float *mean, const float *invstd, const float *gamma,
-                   const float *beta, int32_t relu, float *y, u2mkd_stream_t s) {
-    return bn_apply_impl<float>(x, n, c, mean, invstd, gamma, beta, relu, y, s);
-}
-
-int u2mkd_bn_backward_local(const float *dy, const float *x, int64_t n, int32_t c, const float *mean,
-                            const float *invstd, const float *gamma, const float *beta, int32_t relu, float *partial,
-                            float *sums /*[2c]: dbeta, dgamma of this rank*/, u2mkd_stream_t s) {
-    return bn_backward_local_impl<float>(dy, x, n, c, mean, invstd, gamma, beta, relu, partial, sums, s);
-}
-
-int u2mkd_bn_backward_apply(const float *dy, const float *x, int64_t n, int32_t c, const float *total_n,
-                            const float *mean, const float *invstd, const float *gamma, const float *beta,
-                            int32_t relu, const float *sums /*[2c] summed over ranks*/, float *dx, u2mkd_stream_t s) {
-    return bn_backward_apply_impl<float>(dy, x, n, c, total_n, mean, invstd, gamma, beta, relu, sums, dx, s);
-}
-
-/* the three pieces with the residual branch of a ResidualBlock: y = relu(bn(x) + res); the backward recomputes the mask
- * from x and res and returns dres = the masked dy */
-int u2mkd_bn_apply_res(const float *x, const float *res, int64_t n, int32_t c, const float *mean, const float *invstd,
-                       const float *gamma, const float *beta, int32_t relu, float *y, u2mkd_stream_t s) {
-    return bn_apply_impl<float>(x, n, c, mean, invstd, gamma, beta, relu, y, s, res);
-}
-
-int u2mkd_bn_backward_local_res(const float *dy, const float *x, const float *res, int64_t n, int32_t c, const float *mean,
-                                const float *invstd, const float *gamma, const float *beta, int32_t relu, float *partial,
-                                float *sums, u2mkd_stream_t s) {
-    return bn_backward_local_impl<float>(dy, x, n, c, mean, invstd, gamma, beta, relu, partial, sums, s, res);
-}
-
-int u2mkd_bn_backward_apply_res(const float *dy, const float *x, const float *res, int64_t n, int32_t c, const float *total_n,
-                                const float *mean, const float *invstd, const float *gamma, const float *beta, int32_t relu,
-                                const float *sums, float *dx, float *dres, u2mkd_stream_t s) {
-    return bn_backward_apply_impl<float>(dy, x, n, c, total_n, mean, invstd, gamma, beta, relu, sums, dx, s, res, dres);
-}
-
-/* ---- the same on BF16 rows (x, res, y, dy, dx, dres are bf16 [n, c]; every statistic, parameter and sum fp32) ---- */
-int u2mkd_bn_train_forward_res_bf16(const void *x, const void *res, int64_t n, int32_t c, const float *gamma,
-                                    const float *beta, float eps, float momentum, float *running_mean, float *running_var,
-                                    int64_t *num_batches_tracked, int32_t relu, float *partial, float *mean, float *invstd,
-                                    void *y, u2mkd_stream_t s) {
-    return bn_train_forward_impl<bf16row>(BF(x), BF(res), n, c, gamma, beta, eps, momentum, running_mean, running_var,
-                                          num_batches_tracked, relu, partial, mean, invstd, BFW(y), s);
-}
-
-int u2mkd_bn_eval_forward_res_bf16(const void *x, const void *res, int64_t n, int32_t c, const float *gamma, const float *beta,
-                                   float eps, const float *running_mean, const float *running_var, int32_t relu,
-                                   float *invstd, void *y, u2mkd_stream_t s) {
-    return bn_eval_forward_impl<bf16row>(BF(x), BF(res), n, c, gamma, beta, eps, running_mean, running_var, relu, invstd,
-                                         BFW(y), s);
-}
-
-int u2mkd_bn_backward_res_bf16(const void *dy, const void *x, const void *res, int64_t n, int32_t c, const float *mean,
-                               const float *invstd, const float *gamma, const float *beta, int32_t relu, int32_t training,
-                               float *partial, float *dgamma, float *dbeta, void *dx, void *dres, u2mkd_stream_t s) {
-    return bn_backward_impl<bf16row>(BF(dy), BF(x), BF(res), n, c, mean, invstd, gamma, beta, relu, training, partial, dgamma,
-                                     dbeta, BFW(dx), BFW(dres), s);
-}
-
-int u2mkd_bn_local_stats_bf16(const void *x, int64_t n, int32_t c, float *partial, float *stats, u2mkd_stream_t s) {
-    return bn_local_stats_impl<bf16row>(BF(x), n, c, partial, stats, s);
-}
-
-int u2mkd_bn_apply_bf16(const void *x, int64_t n, int32_t c, const float *mean, const float *invstd, const float *gamma,
-                        const float *beta, int32_t relu, void *y, u2mkd_stream_t s) {
-    return bn_apply_impl<bf16row>(BF(x), n, c, mean, invstd, gamma, beta, relu, BFW(y), s);
-}
-
-int u2mkd_bn_backward_local_bf16(const void *dy, const void *x, int64_t n, int32_t c, const float *mean, const float *invstd,
-                                 const float *gamma, const float *beta, int32_t relu, float *partial, float *sums,
-                                 u2mkd_stream_t s) {
-    return bn_backward_local_impl<bf16row>(BF(dy), BF(x), n, c, mean, invstd, gamma, beta, relu, partial, sums, s);
-}
-
-int u2mkd_bn_backward_apply_bf16(const void *dy, const void *x, int64_t n, int32_t c, const float *total_n, const float *mean,
-                                 const float *invstd, const float *gamma, const float *beta, int32_t relu, const float *sums,
-                                 void *dx, u2mkd_stream_t s) {
-    return bn_backward_apply_impl<bf16row>(BF(dy), BF(x), n, c, total_n, mean, invstd, gamma, beta, relu, sums, BFW(dx), s);
-}
-
-int u2mkd_bn_apply_res_bf16(const void *x, const void *res, int64_t n, int32_t c, const float *mean, const float *invstd,
-                            const float *gamma, const float *beta, int32_t relu, void *y, u2mkd_stream_t s) {
-    return bn_apply_impl<bf16row>(BF(x), n, c, mean, invstd, gamma, beta, relu, BFW(y), s, BF(res));
-}
-
-int u2mkd_bn_backward_local_res_bf16(const void *dy, const void *x, const void *res, int64_t n, int32_t c, const float *mean,
-                                     const float *invstd, const float *gamma, const float *beta, int32_t relu, float *partial,
-                                     float *sums, u2mkd_stream_t s) {
-    return bn_backward_local_impl<bf16row>(BF(dy), BF(x), n, c, mean, invstd, gamma, beta, relu, partial, sums, s, BF(res));
-}
-
-/* u2mkd_bn_backward_local(_res)(_bf16) with a SECOND copy of the sums: `sums` goes into the all_reduce (in place), `keep` [2c]
- * stays this rank's (the parameter gradients, which DDP averages) -- the copy kernel in between is gone.  bf16_rows != 0: dy, x,
- * res are bf16 rows; res may be NULL. */
-int u2mkd_bn_backward_local_keep(const void *dy, const void *x, const void *res, int32_t bf16_rows, int64_t n, int32_t c,
-                                 const float *mean, const float *invstd, const float *gamma, const float *beta, int32_t relu,
-                                 float *partial, float *sums, float *keep, u2mkd_stream_t s) {
-    U2_REQUIRE(keep, "u2mkd_bn_backward_local_keep: null pointer");
+int u2mkd_bn_backward_local(const void *dy, const void *x, const void *res, int32_t bf16_rows, int64_t n, int32_t c,
+                            const float *mean, const float *invstd, const float *gamma, const float *beta, int32_t relu,
+                            float *partial, float *sums, float *keep, u2mkd_stream_t s) {
     if (bf16_rows)
-        return bn_backward_local_impl<bf16row>(BF(dy), BF(x), n, c, mean, invstd, gamma, beta, relu, partial, sums, s, BF(res), keep);
-    return bn_backward_local_impl<float>(reinterpret_cast<const float *>(dy), reinterpret_cast<const float *>(x), n, c, mean, invstd,
-                                         gamma, beta, relu, partial, sums, s, reinterpret_cast<const float *>(res), keep);
+        return bn_backward_local_impl<bf16row>(BF(dy), BF(x), BF(res), n, c, mean, invstd, gamma, beta, relu, partial, sums,
+                                               keep, s);
+    return bn_backward_local_impl<float>(F32(dy), F32(x), F32(res), n, c, mean, invstd, gamma, beta, relu, partial, sums, keep,
+                                         s);
 }
 
-int u2mkd_bn_backward_apply_res_bf16(const void *dy, const void *x, const void *res, int64_t n, int32_t c, const float *total_n,
-                                     const float *mean, const float *invstd, const float *gamma, const float *beta,
-                                     int32_t relu, const float *sums, void *dx, void *dres, u2mkd_stream_t s) {
-    return bn_backward_apply_impl<bf16row>(BF(dy), BF(x), n, c, total_n, mean, invstd, gamma, beta, relu, sums, BFW(dx), s,
-                                           BF(res), BFW(dres));
+int u2mkd_bn_backward_apply(const void *dy, const void *x, const void *res, int32_t bf16_rows, int64_t n, int32_t c,
+                            const float *total_n, const float *mean, const float *invstd, const float *gamma,
+                            const float *beta, int32_t relu, const float *sums, void *dx, void *dres, u2mkd_stream_t s) {
+    if (bf16_rows)
+        return bn_backward_apply_impl<bf16row>(BF(dy), BF(x), BF(res), n, c, total_n, mean, invstd, gamma, beta, relu, sums,
+                                               BFW(dx), BFW(dres), s);
+    return bn_backward_apply_impl<float>(F32(dy), F32(x), F32(res), n, c, total_n, mean, invstd, gamma, beta, relu, sums,
+                                         F32W(dx), F32W(dres), s);
 }
 
 }  // extern "C"

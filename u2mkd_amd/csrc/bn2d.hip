@@ -332,7 +332,9 @@ int u2mkd_bn2d_apply(const float *x, const float *res, int64_t b, int32_t c, int
 
 int u2mkd_bn2d_backward_local(const float *dy, const float *x, const float *res, int64_t b, int32_t c, int64_t hw,
                               const float *mean, const float *invstd, const float *gamma, const float *beta, int32_t relu,
-                              void *workspace, float *sums /*[2c]: dbeta, dgamma of this rank*/, u2mkd_stream_t s) {
+                              void *workspace, float *sums /*[2c]: dbeta, dgamma of this rank*/,
+                              float *keep /*[2c]: a second copy of the sums, may be NULL (as u2mkd_bn_backward_local)*/,
+                              u2mkd_stream_t s) {
     U2_REQUIRE(dy && x && mean && invstd && workspace && sums, "u2mkd_bn2d_backward_local: null pointer");
     U2_REQUIRE(b2_shape_ok(b, c, hw), "u2mkd_bn2d_backward_local: shape [%lld, %d, %lld] out of range", (long long)b, c, (long long)hw);
     const int splits = b2_splits((int)hw, kB2Chunk);
@@ -340,23 +342,8 @@ int u2mkd_bn2d_backward_local(const float *dy, const float *x, const float *res,
     hipLaunchKernelGGL(bn2d_bwd_partial_kernel, dim3((unsigned)(splits * b), (unsigned)c), dim3(kB2Threads), 0, as_stream(s), dy, x,
                        res, c, (int)hw, splits, mean, invstd, gamma, beta, relu, partial);
     hipLaunchKernelGGL(bn2d_bwd_finalize_kernel, dim3((unsigned)c), dim3(64), 0, as_stream(s), partial, (int)(splits * b), sums,
-                       sums + c);
-    return check_launch("u2mkd_bn2d_backward_local");
-}
-
-/* the same with a second copy `keep` [2c] of the sums (u2mkd_bn_backward_local_keep) */
-int u2mkd_bn2d_backward_local_keep(const float *dy, const float *x, const float *res, int64_t b, int32_t c, int64_t hw,
-                                   const float *mean, const float *invstd, const float *gamma, const float *beta, int32_t relu,
-                                   void *workspace, float *sums, float *keep, u2mkd_stream_t s) {
-    U2_REQUIRE(dy && x && mean && invstd && workspace && sums && keep, "u2mkd_bn2d_backward_local_keep: null pointer");
-    U2_REQUIRE(b2_shape_ok(b, c, hw), "u2mkd_bn2d_backward_local_keep: shape [%lld, %d, %lld] out of range", (long long)b, c, (long long)hw);
-    const int splits = b2_splits((int)hw, kB2Chunk);
-    float *partial = reinterpret_cast<float *>(workspace);
-    hipLaunchKernelGGL(bn2d_bwd_partial_kernel, dim3((unsigned)(splits * b), (unsigned)c), dim3(kB2Threads), 0, as_stream(s), dy, x,
-                       res, c, (int)hw, splits, mean, invstd, gamma, beta, relu, partial);
-    hipLaunchKernelGGL(bn2d_bwd_finalize_kernel, dim3((unsigned)c), dim3(64), 0, as_stream(s), partial, (int)(splits * b), sums,
                        sums + c, keep);
-    return check_launch("u2mkd_bn2d_backward_local_keep");
+    return check_launch("u2mkd_bn2d_backward_local");
 }
 
 int u2mkd_bn2d_backward_apply(const float *dy, const float *x, const float *res, int64_t b, int32_t c, int64_t hw,

@@ -285,7 +285,7 @@ using namespace u2mkd;
 
 extern "C" {
 
-int u2mkd_version(void) { return 100; }
+int u2mkd_version(void) { return 101; }
 const char *u2mkd_last_error(void) { return g_err; }
 
 /* `waiter` continues only behind everything queued on `signaler` so far: one event record + one stream wait (what

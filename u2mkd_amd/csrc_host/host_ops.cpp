@@ -29,7 +29,7 @@ inline at::Tensor undef() { return at::Tensor(); }
 
 // ---------------------------------------------------------------------------------------------------- BatchNorm rows
 // functional.BatchNormFunction, fp32 rows: y = [relu](bn(x) [+ res]); statistics / running statistics / step counter inside
-// u2mkd_bn_train_forward_res; backward re-derives the ReLU mask from x.
+// u2mkd_bn_train_forward; backward re-derives the ReLU mask from x.
 struct BatchNormRows : public torch::autograd::Function<BatchNormRows> {
     static at::Tensor forward(AutogradContext *ctx, at::Tensor x, OptTensor gamma, OptTensor beta, OptTensor running_mean,
                               OptTensor running_var, bool training, double momentum, double eps, bool relu, OptTensor counter,
@@ -54,19 +54,20 @@ struct BatchNormRows : public torch::autograd::Function<BatchNormRows> {
             auto partial = at::empty({slabs * 2 * c}, opts);
             mean = at::empty({c}, opts);
             int64_t *cnt = counter.has_value() && counter->defined() ? counter->data_ptr<int64_t>() : nullptr;
-            check(u2mkd_bn_train_forward_res(x.data_ptr<float>(), rp, n, c, cf(gamma), cf(beta), (float)eps, (float)momentum,
-                                             mf(running_mean), mf(running_var), cnt, relu, partial.data_ptr<float>(),
-                                             mean.data_ptr<float>(), invstd.data_ptr<float>(), y.data_ptr<float>(), cur_stream()),
-                  "u2mkd_bn_train_forward_res");
+            check(u2mkd_bn_train_forward(x.data_ptr<float>(), rp, /*bf16_rows=*/0, n, c, cf(gamma), cf(beta), (float)eps,
+                                         (float)momentum, mf(running_mean), mf(running_var), cnt, relu, partial.data_ptr<float>(),
+                                         mean.data_ptr<float>(), invstd.data_ptr<float>(), y.data_ptr<float>(), cur_stream()),
+                  "u2mkd_bn_train_forward");
             // written in place through raw pointers: versions bumped as torch's in-place updates would (eval_bn_affine's cache key)
             for (const OptTensor *t : {&running_mean, &running_var, &counter})
                 if (t->has_value() && (*t)->defined()) torch::autograd::impl::bump_version(**t);
         } else {
             TORCH_CHECK(running_mean.has_value() && running_mean->defined(), "batch_norm_rows: eval mode needs running statistics");
             mean = *running_mean;
-            check(u2mkd_bn_eval_forward_res(x.data_ptr<float>(), rp, n, c, cf(gamma), cf(beta), (float)eps, cf(running_mean),
-                                            cf(running_var), relu, invstd.data_ptr<float>(), y.data_ptr<float>(), cur_stream()),
-                  "u2mkd_bn_eval_forward_res");
+            check(u2mkd_bn_eval_forward(x.data_ptr<float>(), rp, /*bf16_rows=*/0, n, c, cf(gamma), cf(beta), (float)eps,
+                                        cf(running_mean), cf(running_var), relu, invstd.data_ptr<float>(), y.data_ptr<float>(),
+                                        cur_stream()),
+                  "u2mkd_bn_eval_forward");
         }
         ctx->save_for_backward({x, gamma.value_or(undef()), beta.value_or(undef()), mean, invstd, r});
         ctx->saved_data["relu"] = relu;
@@ -87,13 +88,13 @@ struct BatchNormRows : public torch::autograd::Function<BatchNormRows> {
         auto dgb = at::empty({2, c}, opts);                // (dgamma | dbeta in one allocation)
         auto dx = at::empty_like(x);
         at::Tensor dres = res.defined() ? at::empty_like(x) : at::Tensor();
-        check(u2mkd_bn_backward_res(dy.data_ptr<float>(), x.data_ptr<float>(), res.defined() ? res.data_ptr<float>() : nullptr, n, c,
-                                    mean.data_ptr<float>(), invstd.data_ptr<float>(), gamma.defined() ? gamma.data_ptr<float>() : nullptr,
-                                    beta.defined() ? beta.data_ptr<float>() : nullptr, ctx->saved_data["relu"].toBool(),
-                                    ctx->saved_data["training"].toBool(), partial.data_ptr<float>(), dgb[0].data_ptr<float>(),
-                                    dgb[1].data_ptr<float>(), dx.data_ptr<float>(), dres.defined() ? dres.data_ptr<float>() : nullptr,
-                                    cur_stream()),
-              "u2mkd_bn_backward_res");
+        check(u2mkd_bn_backward(dy.data_ptr<float>(), x.data_ptr<float>(), res.defined() ? res.data_ptr<float>() : nullptr,
+                                /*bf16_rows=*/0, n, c, mean.data_ptr<float>(), invstd.data_ptr<float>(),
+                                gamma.defined() ? gamma.data_ptr<float>() : nullptr, beta.defined() ? beta.data_ptr<float>() : nullptr,
+                                ctx->saved_data["relu"].toBool(), ctx->saved_data["training"].toBool(), partial.data_ptr<float>(),
+                                dgb[0].data_ptr<float>(), dgb[1].data_ptr<float>(), dx.data_ptr<float>(),
+                                dres.defined() ? dres.data_ptr<float>() : nullptr, cur_stream()),
+              "u2mkd_bn_backward");
         return {dx, gamma.defined() ? dgb[0] : at::Tensor(), beta.defined() ? dgb[1] : at::Tensor(), at::Tensor(), at::Tensor(),
                 at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), dres};
     }

@@ -123,8 +123,8 @@ class _UpsampledBatchNormReLU(torch.autograd.Function):
         # (one pass; as five element-wise kernels it moved 1.5 GB per step at 6 x 360x640)
         if _ROW_BN:
             y = torch.empty_like(u)
-            L.call('u2mkd_bn_apply', L.ptr(u), u.shape[0], c, L.ptr(mean), L.ptr(invstd), L.ptr(weight), L.ptr(bias), 1, L.ptr(y),
-                   L.stream())
+            L.call('u2mkd_bn_apply', L.ptr(u), None, 0, u.shape[0], c, L.ptr(mean), L.ptr(invstd), L.ptr(weight), L.ptr(bias), 1,
+                   L.ptr(y), L.stream())
         else:
             y = torch.relu((u - mean) * invstd * weight + bias)
         ctx.save_for_backward(x, u, weight, bias, invstd, mean)
@@ -150,8 +150,8 @@ class _UpsampledBatchNormReLU(torch.autograd.Function):
             g = gy * (xhat * weight + bias > 0)
             dbeta, dgamma, du = g.sum(0), (g * xhat).sum(0), g * (weight * invstd)
         elif s_rows:
-            L.call('u2mkd_bn_backward', L.ptr(gy), L.ptr(u), s_rows, cc, L.ptr(mean), L.ptr(invstd), L.ptr(weight), L.ptr(bias), 1, 0,
-                   L.ptr(partial), L.ptr(dgamma), L.ptr(dbeta), L.ptr(du), L.stream())
+            L.call('u2mkd_bn_backward', L.ptr(gy), L.ptr(u), None, 0, s_rows, cc, L.ptr(mean), L.ptr(invstd), L.ptr(weight),
+                   L.ptr(bias), 1, 0, L.ptr(partial), L.ptr(dgamma), L.ptr(dbeta), L.ptr(du), None, L.stream())
         else:
             dgamma.zero_(); dbeta.zero_()
         scale = weight * invstd

@@ -1653,7 +1653,6 @@ class BatchNormFunction(Function):
         # bf16 storage: rows stay bf16 through the BatchNorm (as nn.BatchNorm1d passes half through under the
         # reference's amp), statistics / parameters / gradient sums fp32
         b16 = bf16_rows() or (x.dtype == torch.bfloat16 and _BF16_ROWS)
-        sfx = '_bf16' if b16 else ''
         ctx.in_dtype, ctx.res_dtype = x.dtype, (res.dtype if res is not None else None)
         x = _rows(x, b16)
         n, c = x.shape
@@ -1672,12 +1671,12 @@ class BatchNormFunction(Function):
             slabs = L.load().u2mkd_bn_num_slabs(n)
             partial = torch.empty(max(slabs, 1) * 2 * c, dtype=torch.float32, device=dev)
             mean = torch.empty(c, dtype=torch.float32, device=dev)
-            L.call('u2mkd_bn_train_forward_res' + sfx, L.ptr(x), L.ptr(res), n, c, L.ptr(gamma), L.ptr(beta), float(eps),
+            L.call('u2mkd_bn_train_forward', L.ptr(x), L.ptr(res), int(b16), n, c, L.ptr(gamma), L.ptr(beta), float(eps),
                    float(momentum), L.ptr(running_mean), L.ptr(running_var), L.ptr(counter), int(relu), L.ptr(partial),
                    L.ptr(mean), L.ptr(invstd), L.ptr(y), L.stream())
         else:
             mean = running_mean
-            L.call('u2mkd_bn_eval_forward_res' + sfx, L.ptr(x), L.ptr(res), n, c, L.ptr(gamma), L.ptr(beta), float(eps),
+            L.call('u2mkd_bn_eval_forward', L.ptr(x), L.ptr(res), int(b16), n, c, L.ptr(gamma), L.ptr(beta), float(eps),
                    L.ptr(running_mean), L.ptr(running_var), int(relu), L.ptr(invstd), L.ptr(y), L.stream())
         ctx.save_for_backward(x, gamma, beta, mean, invstd, res)
         ctx.relu, ctx.training = bool(relu), bool(training)
@@ -1696,9 +1695,9 @@ class BatchNormFunction(Function):
         dbeta = torch.empty(c, dtype=torch.float32, device=dev)
         dx = torch.empty_like(x)
         dres = torch.empty_like(x) if res is not None else None
-        L.call('u2mkd_bn_backward_res_bf16' if b16 else 'u2mkd_bn_backward_res', L.ptr(dy), L.ptr(x), L.ptr(res), n, c,
-               L.ptr(mean), L.ptr(invstd), L.ptr(gamma), L.ptr(beta), int(ctx.relu), int(ctx.training), L.ptr(partial),
-               L.ptr(dgamma), L.ptr(dbeta), L.ptr(dx), L.ptr(dres), L.stream())
+        L.call('u2mkd_bn_backward', L.ptr(dy), L.ptr(x), L.ptr(res), int(b16), n, c, L.ptr(mean), L.ptr(invstd), L.ptr(gamma),
+               L.ptr(beta), int(ctx.relu), int(ctx.training), L.ptr(partial), L.ptr(dgamma), L.ptr(dbeta), L.ptr(dx),
+               L.ptr(dres), L.stream())
         if dx.dtype != ctx.in_dtype:
             dx = dx.to(ctx.in_dtype)
         if dres is not None and dres.dtype != ctx.res_dtype:
@@ -1756,7 +1755,6 @@ class SyncBatchNormFunction(Function):
         import torch.distributed as dist
         L.require_cuda(x)
         b16 = bf16_rows() or (x.dtype == torch.bfloat16 and _BF16_ROWS)
-        sfx = '_bf16' if b16 else ''
         ctx.in_dtype = x.dtype
         x = _rows(x, b16)
         if res is not None:          # relu(bn(x) + res): the tail of a ResidualBlock inside the apply pass
@@ -1768,7 +1766,7 @@ class SyncBatchNormFunction(Function):
         slabs = L.load().u2mkd_bn_num_slabs(n)
         partial = torch.empty(max(slabs, 1) * 2 * c, dtype=torch.float32, device=dev)
         stats = torch.empty(2 * c + 1, dtype=torch.float32, device=dev)
-        L.call('u2mkd_bn_local_stats' + sfx, L.ptr(x), n, c, L.ptr(partial), L.ptr(stats), st)
+        L.call('u2mkd_bn_local_stats', L.ptr(x), int(b16), n, c, L.ptr(partial), L.ptr(stats), st)
         note_collective('all_gather', stats)
         if world > 1:
             gathered = torch.empty(world, 2 * c + 1, dtype=torch.float32, device=dev)
@@ -1778,15 +1776,11 @@ class SyncBatchNormFunction(Function):
         # mean | invstd | total in one allocation; the step counter is bumped inside the merge launch
         mit = torch.empty(2 * c + 1, dtype=torch.float32, device=dev)
         mean, invstd, total = mit[:c], mit[c:2 * c], mit[2 * c:]
-        L.call('u2mkd_bn_merge_stats_counted', L.ptr(gathered), world, c, float(eps), float(momentum), L.ptr(running_mean),
+        L.call('u2mkd_bn_merge_stats', L.ptr(gathered), world, c, float(eps), float(momentum), L.ptr(running_mean),
                L.ptr(running_var), L.ptr(mean), L.ptr(invstd), L.ptr(total), L.ptr(counter), L.stream())
         y = torch.empty_like(x)
-        if res is None:
-            L.call('u2mkd_bn_apply' + sfx, L.ptr(x), n, c, L.ptr(mean), L.ptr(invstd), L.ptr(gamma), L.ptr(beta), int(relu),
-                   L.ptr(y), L.stream())
-        else:
-            L.call('u2mkd_bn_apply_res' + sfx, L.ptr(x), L.ptr(res), n, c, L.ptr(mean), L.ptr(invstd), L.ptr(gamma),
-                   L.ptr(beta), int(relu), L.ptr(y), L.stream())
+        L.call('u2mkd_bn_apply', L.ptr(x), L.ptr(res), int(b16), n, c, L.ptr(mean), L.ptr(invstd), L.ptr(gamma), L.ptr(beta),
+               int(relu), L.ptr(y), L.stream())
         ctx.save_for_backward(x, gamma, beta, mean, invstd, total, res)
         ctx.relu, ctx.group, ctx.world = bool(relu), group, world
         return y
@@ -1796,7 +1790,6 @@ class SyncBatchNormFunction(Function):
         import torch.distributed as dist
         x, gamma, beta, mean, invstd, total, res = ctx.saved_tensors
         b16 = x.dtype == torch.bfloat16
-        sfx = '_bf16' if b16 else ''
         dy = _rows(dy, b16)
         n, c = x.shape
         dev = x.device
@@ -1806,22 +1799,17 @@ class SyncBatchNormFunction(Function):
         # DDP averages them)
         both = torch.empty(2, 2 * c, dtype=torch.float32, device=dev)
         sums, local = both[0], both[1]
-        L.call('u2mkd_bn_backward_local_keep', L.ptr(dy), L.ptr(x), L.ptr(res), int(b16), n, c, L.ptr(mean), L.ptr(invstd),
+        L.call('u2mkd_bn_backward_local', L.ptr(dy), L.ptr(x), L.ptr(res), int(b16), n, c, L.ptr(mean), L.ptr(invstd),
                L.ptr(gamma), L.ptr(beta), int(ctx.relu), L.ptr(partial), L.ptr(sums), L.ptr(local), L.stream())
         note_collective('all_reduce', sums)
         if ctx.world > 1:
             _sum_over_ranks(sums, ctx.group)
         dx = torch.empty_like(x)
-        dres = None
-        if res is None:
-            L.call('u2mkd_bn_backward_apply' + sfx, L.ptr(dy), L.ptr(x), n, c, L.ptr(total), L.ptr(mean), L.ptr(invstd),
-                   L.ptr(gamma), L.ptr(beta), int(ctx.relu), L.ptr(sums), L.ptr(dx), L.stream())
-        else:
-            dres = torch.empty_like(x)
-            L.call('u2mkd_bn_backward_apply_res' + sfx, L.ptr(dy), L.ptr(x), L.ptr(res), n, c, L.ptr(total), L.ptr(mean),
-                   L.ptr(invstd), L.ptr(gamma), L.ptr(beta), int(ctx.relu), L.ptr(sums), L.ptr(dx), L.ptr(dres), L.stream())
-            if dres.dtype != ctx.res_dtype:
-                dres = dres.to(ctx.res_dtype)
+        dres = torch.empty_like(x) if res is not None else None
+        L.call('u2mkd_bn_backward_apply', L.ptr(dy), L.ptr(x), L.ptr(res), int(b16), n, c, L.ptr(total), L.ptr(mean),
+               L.ptr(invstd), L.ptr(gamma), L.ptr(beta), int(ctx.relu), L.ptr(sums), L.ptr(dx), L.ptr(dres), L.stream())
+        if dres is not None and dres.dtype != ctx.res_dtype:
+            dres = dres.to(ctx.res_dtype)
         if dx.dtype != ctx.in_dtype:
             dx = dx.to(ctx.in_dtype)
         return (dx, local[c:] if gamma is not None else None, local[:c] if beta is not None else None,
