@@ -115,6 +115,16 @@ int u2mkd_downsample_keys(const int32_t *coords /*[n,4]*/, int64_t n, int32_t sx
 int u2mkd_downsample_keys_checked(const int32_t *coords /*[n,4]*/, int64_t n, int32_t sx, int32_t sy, int32_t sz,
                                   int64_t *keys /*[n]*/, int32_t *range_flag, u2mkd_stream_t s);
 int u2mkd_unpack_keys(const int64_t *keys, int64_t n, int32_t *coords /*[n,4]*/, u2mkd_stream_t s);
+/* F.spdownsample where some stride[a] is neither 1 nor kernel_size[a] (k = 3, s = 2): the outputs are the distinct kept
+ * candidates c + offset over all input rows c and window offsets -- kept = on every axis a multiple of
+ * ss[a] = s[a] * ts[a] and >= cmin[a] (device int32 [3]: the minimum input coordinate per axis, all batches together).  A
+ * row has at most m = prod_a ceil(k[a] / s[a]) of them (8 of the 27 for k = 3, s = 2), found arithmetically; the kernel
+ * writes their keys (the pack above) into keys[i][0..m); a slot without a kept candidate gets INT64_MAX (sorts last,
+ * leaves *range_flag alone), a kept candidate outside the packed range gets INT64_MAX too and sets *range_flag
+ * (device int32, caller-zeroed, may be NULL).  The caller sorts / uniques the n * m keys and drops INT64_MAX.    */
+int u2mkd_downsample_keys_general(const int32_t *coords /*[n,4]*/, int64_t n, int32_t tsx, int32_t tsy, int32_t tsz, int32_t kx,
+                                  int32_t ky, int32_t kz, int32_t sx, int32_t sy, int32_t sz, const int32_t *cmin /*[3]*/,
+                                  int32_t m, int64_t *keys /*[n,m]*/, int32_t *range_flag, u2mkd_stream_t s);
 /* voxel of every point at tensor stride s: (floor(xyz / s) * s, (int)b) from float (x, y, z, b) rows -- the hash
  * input of point_to_voxel / voxel_to_point (core/models/utils.py:43-47,86-90), one launch instead of seven.    */
 int u2mkd_floor_coords(const float *pc /*[n,4]*/, int64_t n, int32_t stride, int32_t *out /*[n,4]*/, u2mkd_stream_t s);

@@ -243,6 +243,62 @@ __global__ void downsample_keys_kernel(const int4 *__restrict__ coords, int64_t 
     keys[i] = ((int64_t)c.w << 54) | ((int64_t)(x + bias) << 36) | ((int64_t)(y + bias) << 18) | (int64_t)(z + bias);
 }
 
+// ---- downsample keys, general branch (stride[a] not in {1, kernel[a]}: k = 3, s = 2) ---------------------------
+// The outputs of such a conv are the kept candidates c + offset over all input rows c and window offsets: kept = on
+// every axis a multiple of ss = stride * tensor_stride and >= the minimum input coordinate of that axis.  On one axis
+// the window is c + o * ts for o in [lo, lo + ks), and the multiples of ss inside it are first, first + ss, ... with
+// first = ss * ceil((c + lo * ts) / ss): at most m = ceil(ks / stride) of them, and they are window members iff c is a
+// multiple of ts.  One thread per input row writes its mx * my * mz candidates' keys (the pack above) into its slots
+// of keys [n, mx * my * mz]; a slot without a kept candidate gets the padding key INT64_MAX, which sorts last and
+// leaves the range flag alone; a kept candidate that cannot be packed gets the same key and raises *range_flag.
+struct DownAxes {
+    int ts[3], ks[3], ss[3], m[3];
+};
+
+__global__ void downsample_keys_general_kernel(const int4 *__restrict__ coords, int64_t n, DownAxes ax,
+                                               const int32_t *__restrict__ cmin, int64_t *__restrict__ keys,
+                                               int32_t *__restrict__ range_flag) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int4 c = coords[i];
+    const int cc[3] = {c.x, c.y, c.z};
+    int64_t first[3], last[3];          // first kept multiple of ss on the axis; upper end of the window (last < first: none)
+    for (int a = 0; a < 3; ++a) {
+        const int64_t ts = ax.ts[a], ss = ax.ss[a];
+        const int64_t lo = (int64_t)cc[a] + (int64_t)(-((ax.ks[a] + 1) / 2) + 1) * ts;      // (-ks // 2 + 1) * ts
+        int64_t q = lo / ss;
+        if (lo % ss != 0 && lo > 0) ++q;                                                    // ceil
+        first[a] = q * ss;
+        last[a] = cc[a] % ts == 0 ? lo + (int64_t)(ax.ks[a] - 1) * ts : first[a] - 1;
+        const int64_t mn = cmin[a];
+        if (first[a] < mn) first[a] += (mn - first[a] + ss - 1) / ss * ss;                  // cut below the minimum
+    }
+    const int64_t bias = 1 << 17, lim = 1 << 17;
+    const int m = ax.m[0] * ax.m[1] * ax.m[2];
+    int64_t *row = keys + i * m;
+    const bool b_ok = c.w >= 0 && c.w < 512;
+    bool bad = false;
+    int slot = 0;
+    for (int ix = 0; ix < ax.m[0]; ++ix) {
+        const int64_t x = first[0] + ix * (int64_t)ax.ss[0];
+        for (int iy = 0; iy < ax.m[1]; ++iy) {
+            const int64_t y = first[1] + iy * (int64_t)ax.ss[1];
+            for (int iz = 0; iz < ax.m[2]; ++iz, ++slot) {
+                const int64_t z = first[2] + iz * (int64_t)ax.ss[2];
+                int64_t key = INT64_MAX;
+                if (x <= last[0] && y <= last[1] && z <= last[2]) {
+                    if (b_ok && x >= -lim && x < lim && y >= -lim && y < lim && z >= -lim && z < lim)
+                        key = ((int64_t)c.w << 54) | ((x + bias) << 36) | ((y + bias) << 18) | (z + bias);
+                    else
+                        bad = true;
+                }
+                row[slot] = key;
+            }
+        }
+    }
+    if (bad && range_flag) *range_flag = 1;
+}
+
 __global__ void table_clear_kernel(TableView t, int64_t cap) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= cap) return;
@@ -488,6 +544,31 @@ int u2mkd_downsample_keys_checked(const int32_t *coords, int64_t n, int32_t sx, 
 int u2mkd_downsample_keys(const int32_t *coords, int64_t n, int32_t sx, int32_t sy, int32_t sz, int64_t *keys,
                           u2mkd_stream_t s) {
     return u2mkd_downsample_keys_checked(coords, n, sx, sy, sz, keys, nullptr, s);
+}
+
+int u2mkd_downsample_keys_general(const int32_t *coords, int64_t n, int32_t tsx, int32_t tsy, int32_t tsz, int32_t kx, int32_t ky,
+                                  int32_t kz, int32_t sx, int32_t sy, int32_t sz, const int32_t *cmin, int32_t m, int64_t *keys,
+                                  int32_t *range_flag, u2mkd_stream_t s) {
+    const int32_t ts[3] = {tsx, tsy, tsz}, ks[3] = {kx, ky, kz}, st[3] = {sx, sy, sz};
+    DownAxes ax;
+    int64_t slots = 1;
+    for (int a = 0; a < 3; ++a) {
+        U2_REQUIRE(ts[a] > 0 && st[a] > 0, "u2mkd_downsample_keys_general: strides must be positive");
+        U2_REQUIRE(ks[a] >= 1 && ks[a] <= 32, "u2mkd_downsample_keys_general: kernel size outside 1..32");
+        U2_REQUIRE((int64_t)ts[a] * st[a] < (1 << 18) && (int64_t)ts[a] * ks[a] < (1 << 18),
+                   "u2mkd_downsample_keys_general: stride * tensor_stride outside the packed key range");
+        ax.ts[a] = ts[a];
+        ax.ks[a] = ks[a];
+        ax.ss[a] = ts[a] * st[a];
+        ax.m[a] = (ks[a] + st[a] - 1) / st[a];
+        slots *= ax.m[a];
+    }
+    U2_REQUIRE(slots == m, "u2mkd_downsample_keys_general: m = %d, but prod ceil(kernel / stride) = %d", (int)m, (int)slots);
+    if (n == 0) return 0;
+    U2_REQUIRE(coords && cmin && keys, "u2mkd_downsample_keys_general: null pointer");
+    hipLaunchKernelGGL(downsample_keys_general_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, as_stream(s),
+                       reinterpret_cast<const int4 *>(coords), n, ax, cmin, keys, range_flag);
+    return check_launch("u2mkd_downsample_keys_general");
 }
 
 int u2mkd_floor_coords(const float *pc, int64_t n, int32_t stride, int32_t *out, u2mkd_stream_t s) {

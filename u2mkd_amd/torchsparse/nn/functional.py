@@ -328,15 +328,16 @@ def calc_ti_weights(coords, idx_query, scale=1):
 
 # --------------------------------------------------------------- downsample
 def spdownsample(coords, stride=2, kernel_size=2, tensor_stride=1):
-    """Output coordinates of a strided conv, sorted by (b,x,y,z) (Appendix A-4).
-    Only the stride[k] in {1, kernel_size[k]} branch is on the U2MKD path."""
+    """Output coordinates of a strided conv, int32 [n_out, 4] sorted by (b,x,y,z) (Appendix A-4).
+    stride[k] in {1, kernel_size[k]} on every axis (k = 2, s = 2: the form U2MKD uses): the inputs floored to multiples of
+    stride * tensor_stride.  Any other stride (k = 3, s = 2; kernel (3,3,3) with stride (2,2,1)): the general branch
+    (:func:`_spdownsample_general`)."""
     L.require_cuda(coords)
     stride = make_ntuple(stride, ndim=3)
     kernel_size = make_ntuple(kernel_size, ndim=3)
     tensor_stride = make_ntuple(tensor_stride, ndim=3)
     if not all(stride[k] in (1, kernel_size[k]) for k in range(3)):
-        raise NotImplementedError('spdownsample: only stride in {1, kernel_size} is supported '
-                                  '(the only form U2MKD uses: k=2, s=2)')
+        return _spdownsample_general(coords, stride, kernel_size, tensor_stride)
     ss = [stride[k] * tensor_stride[k] for k in range(3)]
     coords = _i32(coords).contiguous()
     n = coords.shape[0]
@@ -351,6 +352,45 @@ def spdownsample(coords, stride=2, kernel_size=2, tensor_stride=1):
     elif n:
         _check_range_flag(flag)
     out = torch.empty(uniq.shape[0], 4, dtype=torch.int32, device=coords.device)
+    L.call('u2mkd_unpack_keys', L.ptr(uniq), uniq.shape[0], L.ptr(out), L.stream())
+    return out
+
+
+_PAD_KEY = (1 << 63) - 1
+
+
+def _spdownsample_general(coords, stride, kernel_size, tensor_stride):
+    """torchsparse v1.4.0's general branch of spdownsample: every input row plus every kernel offset
+    (get_kernel_offsets(kernel_size, tensor_stride)) is a candidate; a candidate is kept iff on every axis it is a multiple of
+    stride * tensor_stride and not below the smallest input coordinate of that axis (one minimum for all batches); the output
+    is the set of kept candidates.  ``n_out`` may exceed ``n``; an axis with stride 1 and kernel 3 dilates the set.
+    torchsparse repeats the rows K times, masks and runs unique(dim=0) on [K * n, 4]; here a row's kept candidates -- at most
+    M = prod ceil(kernel / stride) per row, 8 of the 27 for k = 3, s = 2 -- are written as packed keys by one launch
+    (u2mkd_downsample_keys_general) and M * n int64 keys are sorted.  The minimum stays on the device."""
+    if any(s < 1 for s in stride):
+        raise ValueError(f'spdownsample: stride {stride} must be positive')
+    coords = _i32(coords).contiguous()
+    n = coords.shape[0]
+    dev = coords.device
+    if n == 0:
+        return torch.empty(0, 4, dtype=torch.int32, device=dev)
+    m = 1
+    for k in range(3):
+        m *= -(-kernel_size[k] // stride[k])
+    cmin = torch.amin(coords[:, :3], 0)
+    # one slot past the rows' holds the padding key: the sorted unique keys then always end with it, and dropping the last one
+    # needs no look at the data
+    keys = torch.empty(n * m + 1, dtype=torch.int64, device=dev)
+    keys[n * m:].fill_(_PAD_KEY)
+    flag = _range_flag(dev)
+    L.call('u2mkd_downsample_keys_general', L.ptr(coords), n, *tensor_stride, *kernel_size, *stride, L.ptr(cmin), m, L.ptr(keys),
+           L.ptr(flag), L.stream())
+    uniq = torch.unique(keys)[:-1]  # sorted int64 == (b,x,y,z) lexicographic
+    if _deferred()[0]:
+        _deferred().append(flag)
+    else:
+        _check_range_flag(flag)
+    out = torch.empty(uniq.shape[0], 4, dtype=torch.int32, device=dev)
     L.call('u2mkd_unpack_keys', L.ptr(uniq), uniq.shape[0], L.ptr(out), L.stream())
     return out
 
