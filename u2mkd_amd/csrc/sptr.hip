@@ -878,9 +878,12 @@ int u2mkd_sptr_quant_coords(const float *xyz, const int32_t *sort_idx, int64_t n
 
 // Lanes per (token, head).  The window length is only known on the device; what the host knows is the token count
 // and the branch: the cubic windows hold a few tokens at every stage, the spherical windows grow as the token count
-// shrinks (coarser stages, wider cones).  U2MKD_SPTR_SPLIT = 1 / 2 / 4 / 8 / 16 overrides (A/B runs).
+// shrinks (coarser stages, wider cones).  U2MKD_SPTR_SPLIT = 1 / 2 / 4 / 8 / 16 overrides, on either branch (A/B runs,
+// tests/test_gpu_sptr_splits.py); it is read on every call, so it must not change between a backward and the
+// u2mkd_sptr_table_reduce that sums its slabs.
 static int sptr_split(int64_t n, float split_a) {
-    static const int forced = [] { const char *e = getenv("U2MKD_SPTR_SPLIT"); return e ? atoi(e) : 0; }();
+    const char *e = getenv("U2MKD_SPTR_SPLIT");
+    const int forced = e ? atoi(e) : 0;
     if (forced == 1 || forced == 2 || forced == 4 || forced == 8 || forced == 16) return forced;
     if (split_a <= 0.f) return 1;
     return n < 12000 ? 16 : n < 24000 ? 8 : n < 48000 ? 4 : 2;
@@ -1006,8 +1009,9 @@ int u2mkd_sptr_attention_backward_strided(const float *q, const float *k, const 
                            delta, sort_idx, wstart, wlen, qc, rad, tq, tk, tv, L, rc, n, h, dk, dv, slabs, ly);          \
     } while (0)
     // S > 1: both roles in one launch (see sptr_bwd_both_kernel); S = 1 (128 tokens' strips per workgroup: 137 + 95 KB of LDS, the
-    // grid already covers the chip) keeps the two launches.  U2MKD_SPTR_BWD_MERGE=0: two launches everywhere (A/B).
-    static const bool merge = [] { const char *e = getenv("U2MKD_SPTR_BWD_MERGE"); return !(e && e[0] == '0'); }();
+    // grid already covers the chip) keeps the two launches.  U2MKD_SPTR_BWD_MERGE=0: two launches everywhere (A/B; read on every call).
+    const char *merge_env = getenv("U2MKD_SPTR_BWD_MERGE");
+    const bool merge = !(merge_env && merge_env[0] == '0');
     const size_t lds_b = lds_q > lds_k ? lds_q : lds_k;
 #define U2_SPTR_BOTH(SS)                                                                                                 \
     do {                                                                                                                 \
