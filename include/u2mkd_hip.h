@@ -175,6 +175,10 @@ int u2mkd_conv_forward_sorted(const float *in, int64_t n_in, int32_t cin, const 
  *       likewise with one scale per tensor (16-byte trailer {scale, 1/scale, 0, 0} behind each orientation's fragments); the
  *       three partial products above 2^-24 relative are accumulated in fp32 by v_mfma_f32_16x16x16_f16 and the scales taken
  *       out exactly -- the accuracy class of bf16x3 at half its matrix instructions; inputs and outputs stay fp32;
+ *   3 = BF16 STORAGE (u2mkd_*_bf16 below): ONE plane of the weights rounded to bf16, 2 bytes per weight, no trailer; the rows are
+ *       bf16 too and a 32-channel product is two v_mfma_f32_16x16x16_bf16;
+ *   5 = FP16 STORAGE (u2mkd_*_f16 below): the byte count and layout of 3 with every weight cast float -> _Float16 (round to
+ *       nearest even, no scale, no trailer); fp16 rows, a 32-channel product is two v_mfma_f32_16x16x16_f16;
  *   0 = the library default (bf16x3; environment U2MKD_CONV_ARITH=f32 selects 1).
  * u2mkd_conv_tiles_arith(cin, cout, k): the code the host side should pass for a layer of fp32 rows -- 4 where the f16x2
  * form exists, else 2; U2MKD_CONV_ARITH=f32 / bf16x3 force 1 / 2; 0 = not a tile-kernel layer.
@@ -192,7 +196,8 @@ int u2mkd_weight_fragments(const float *w, int32_t k, int32_t rows, int32_t cols
  * behind the optimizer instead of one latency-bound launch per weight in front of its first convolution.
  * jobs: DEVICE int64 [n_jobs][8] = {w (device address of the fp32 [k,rows,cols] weight), wf (device address of
  * 2 x u2mkd_weight_fragments_bytes(k, rows, cols, arith) bytes: [transpose = 1 | transpose = 0]), first unit, k, rows,
- * cols, planes (3 for arith 2 = bf16x3, 1 for arith 3 = one bf16 plane, 2 for arith 4 = f16x2), 0}; job j owns the units
+ * cols, planes (3 for arith 2 = bf16x3, 1 for arith 3 or 5 = one 16-bit plane, 2 for arith 4 = f16x2), the 16-bit type of a
+ * one-plane job (0 = bf16, arith 3; 1 = fp16, arith 5; 0 for the other arithmetics)}; job j owns the units
  * [first_j, first_j + 2 k rows cols / 512), consecutive from 0; total_units = their sum.  Replaces nothing in the
  * reference (torchsparse reads `kernel` as it is); it is the price of the MFMA fragment order.            */
 int u2mkd_weight_fragments_batch(const int64_t *jobs, int32_t n_jobs, int64_t total_units, u2mkd_stream_t s);
@@ -290,7 +295,8 @@ int u2mkd_kmap_rowmask(const int32_t *nbr /*[k,n_out]*/, int64_t n_out, int32_t 
 /* BF16 STORAGE variants (BASELINE.json configs[4]; torchsparse runs its conv in half precision under autocast,
  * custom_fwd(cast_inputs=half)): feature rows in and out are bf16 [n, c] (2 bytes per
  * channel: half the gather bytes), weights = ONE bf16 plane in fragment order (u2mkd_weight_fragments arith = 3,
- * u2mkd_weight_fragments_bytes(.., 3) = 2 bytes per weight), products on v_mfma_f32_16x16x32_bf16 with fp32
+ * u2mkd_weight_fragments_bytes(.., 3) = 2 bytes per weight), a 32-channel product = two v_mfma_f32_16x16x16_bf16 (the
+ * gfx942 form; gfx950's K = 32 instruction is not issued, see csrc/conv_internal.h) with fp32
  * accumulation, every output rounded to bf16 once.  The weight gradient reads bf16 rows and returns fp32 (the
  * optimizer's master dtype).  Parity statements stay in fp32; these are held against the fp32 kernels on
  * bf16-rounded inputs (tests/test_gpu_torchsparse_ops.py).                                                     */
@@ -301,6 +307,27 @@ int u2mkd_conv_forward_tiles_bf16(const void *in /*bf16 [n_in,cin]*/, int64_t n_
 int u2mkd_conv_wgrad_pairs_bf16(const void *a /*bf16 [.,ca]*/, int32_t ca, const void *b /*bf16 [.,cb]*/, int32_t cb,
                                 const int32_t *pairs, const int32_t *plan, int64_t n_rows, int32_t k, int32_t swap,
                                 void *workspace, size_t workspace_bytes, float *dw /*[k,ca,cb] fp32*/, u2mkd_stream_t s);
+/* FP16 STORAGE variants (the reference's amp mode: autocast to half + GradScaler, core/nusc_trainers.py:285): the bf16 entries
+ * above and below with fp16 rows (_Float16 [n, c]) in and out, the same argument lists, wf = the ONE fp16 plane of
+ * u2mkd_weight_fragments arith = 5, a 32-channel product = two v_mfma_f32_16x16x16_f16 (the double-K f16 instruction is never
+ * issued), fp32 accumulation, every stored row value (outputs and the pair schedule's scratch rows y) rounded to nearest even
+ * once.  An fp32 result beyond fp16's range is stored as +-inf, as tensor.half() does, never saturated, and inf / NaN in rows
+ * propagate into the outputs, dX and dW: GradScaler finds an overflowed step by its non-finite gradients.  Weight gradients
+ * are fp32.  Held against the fp32 kernels on fp16-rounded inputs (tests/test_gpu_f16_rows.py).                            */
+int u2mkd_conv_forward_tiles_f16(const void *in /*fp16 [n_in,cin]*/, int64_t n_in, int32_t cin, const void *wf, int32_t cout,
+                                 const int32_t *nbr_sorted, const int32_t *order, const int32_t *items,
+                                 const int32_t *n_items, int64_t n_out, int32_t k, int32_t kflip,
+                                 void *out /*fp16 [n_out,cout]*/, u2mkd_stream_t s);
+int u2mkd_conv_wgrad_pairs_f16(const void *a /*fp16 [.,ca]*/, int32_t ca, const void *b /*fp16 [.,cb]*/, int32_t cb,
+                               const int32_t *pairs, const int32_t *plan, int64_t n_rows, int32_t k, int32_t swap,
+                               void *workspace, size_t workspace_bytes, float *dw /*[k,ca,cb] fp32*/, u2mkd_stream_t s);
+int u2mkd_conv_forward_pairs_f16(const void *in /*fp16 [n_in,cin]*/, int64_t n_in, int32_t cin, const void *wf, int32_t cout,
+                                  const int32_t *pair_idx, const int32_t *tile_k, const int32_t *meta, int64_t capacity,
+                                  int32_t k, void *y /*fp16 [capacity,cout]*/, u2mkd_stream_t s);
+int u2mkd_linear_forward_f16(const void *x /*fp16 [n,cin]*/, int64_t n, int32_t cin, const void *wf, int32_t cout,
+                             const float *bias /*[cout] or NULL*/, void *y /*fp16 [n,cout]*/, u2mkd_stream_t s);
+int u2mkd_pairs_gather_sum_f16(const void *y /*fp16*/, const int32_t *pos /*[n_rows,k]*/, int64_t n_rows, int32_t k,
+                               int32_t cout, void *out /*fp16 [n_rows,cout]*/, u2mkd_stream_t s);
 /* The wide layers (cin * cout >= 8192), nn.Linear and the pair schedule's gather-sum on bf16 rows (csrc/conv_px3.hip B16):
  * u2mkd_conv_forward_pairs_x3 / u2mkd_linear_forward_x3 / u2mkd_pairs_gather_sum with bf16 rows in and out (the scratch
  * rows y are bf16 too), wf = the arith-3 fragments (u2mkd_weight_fragments: conv forward transpose = 1, input gradient /
@@ -399,6 +426,14 @@ int u2mkd_devoxelize_forward_bf16(const void *feats /*bf16 [nv,c]*/, const int32
 int u2mkd_segment_sum_bf16(const void *src /*bf16 [*,c]*/, int32_t c, const int32_t *entry_row /*[E]*/,
                            const float *entry_w /*[E] or NULL*/, const int32_t *seg_offsets /*[nv+1]*/, int64_t nv,
                            int32_t mean, void *out /*bf16 [nv,c]*/, u2mkd_stream_t s);
+/* The same three on FP16 rows (fp16 storage, see u2mkd_conv_forward_tiles_f16): a sum beyond fp16's range is stored as +-inf. */
+int u2mkd_voxelize_backward_f16(const void *grad_out /*fp16 [nv,c]*/, const int32_t *idx, const int32_t *counts, int64_t n,
+                                int64_t nv, int32_t c, void *grad_feats /*fp16 [n,c]*/, u2mkd_stream_t s);
+int u2mkd_devoxelize_forward_f16(const void *feats /*fp16 [nv,c]*/, const int32_t *idx /*[n,8]*/, const float *w /*[n,8]*/,
+                                 int64_t n, int32_t c, void *out /*fp16 [n,c]*/, u2mkd_stream_t s);
+int u2mkd_segment_sum_f16(const void *src /*fp16 [*,c]*/, int32_t c, const int32_t *entry_row /*[E]*/,
+                          const float *entry_w /*[E] or NULL*/, const int32_t *seg_offsets /*[nv+1]*/, int64_t nv,
+                          int32_t mean, void *out /*fp16 [nv,c]*/, u2mkd_stream_t s);
 /* The entry lists u2mkd_segment_sum walks, built in one call (csrc/csr.hip): entries e with key[e] in [0, nv) grouped by
  * key, ascending e inside a group -- bit-identical to a stable argsort by key, by a counting sort (histogram, scan,
  * placement, per-segment sort of the entry ids).  order [n_entries] (the first seg[nv] entries are live, the rest 0),
@@ -558,11 +593,15 @@ int u2mkd_l2c_finish(const int32_t *order_d, const int32_t *seg_d, const int32_t
  * `partial`, [u2mkd_bn_num_slabs(n), 2, c] floats, merged in slab order).
  * gamma / beta / running_* may be NULL.  relu != 0 fuses max(., 0) (backward re-derives the
  * mask from x).  One entry per pass; what varies between the layers is an argument:
- *   bf16_rows            the dtype of the ROWS x, res, y, dy, dx, dres [n, c]: 0 = fp32, != 0 = bf16 (BASELINE.json configs[4];
- *                        under autocast the reference's nn.BatchNorm1d takes and returns half rows while its statistics stay
- *                        fp32).  gamma, beta, running statistics, mean [c], invstd [c], partial, dgamma [c], dbeta [c], stats
- *                        and sums are fp32 either way; a bf16 value is rounded once, at its store, and the backward recomputes
- *                        the ReLU mask from the bf16 x with the forward's fp32 expression, so the two passes agree on it.
+ *   row_dtype            the dtype of the ROWS x, res, y, dy, dx, dres [n, c]: 0 = fp32, 1 = bf16 (BASELINE.json configs[4]),
+ *                        2 = fp16 (the reference's amp mode; under autocast its nn.BatchNorm1d takes and returns half rows
+ *                        while its statistics stay fp32); any other value is an error (u2mkd_last_error).  Until fp16 rows
+ *                        arrived the argument was a flag, != 0 = bf16: every caller in this tree (torchsparse/nn/functional.py,
+ *                        pixel_head.py, csrc_host/host_ops.cpp, tools/, tests/) passes 0 or 1, which mean what they meant.
+ *                        gamma, beta, running statistics, mean [c], invstd [c], partial, dgamma [c], dbeta [c], stats
+ *                        and sums are fp32 in every case; a 16-bit value is rounded once, at its store (fp16: beyond its range
+ *                        +-inf), and the backward recomputes the ReLU mask from the stored x with the forward's fp32 expression,
+ *                        so the two passes agree on it.
  *   res / dres           may be NULL.  The tail of a ResidualBlock (core/models/build_blocks.py:80-83: relu(net(x) +
  *                        downsample(x))) inside the BatchNorm passes: y = relu(bn(x) + res) forward; the backward masks dy with
  *                        (bn(x) + res > 0), returns it as dres (the gradient of the residual branch) and continues with the
@@ -575,7 +614,7 @@ int u2mkd_l2c_finish(const int32_t *order_d, const int32_t *seg_d, const int32_t
  *                        caller's all_reduce in place, `keep` stays this rank's (the parameter gradients, which DDP averages)
  *                        -- replaces the copy between the two.                                                              */
 int64_t u2mkd_bn_num_slabs(int64_t n);
-int u2mkd_bn_train_forward(const void *x, const void *res, int32_t bf16_rows, int64_t n, int32_t c, const float *gamma,
+int u2mkd_bn_train_forward(const void *x, const void *res, int32_t row_dtype, int64_t n, int32_t c, const float *gamma,
                            const float *beta, float eps, float momentum, float *running_mean, float *running_var,
                            int64_t *num_batches_tracked, int32_t relu, float *partial, float *mean /*[c] out*/,
                            float *invstd /*[c] out*/, void *y, u2mkd_stream_t s);
@@ -587,10 +626,10 @@ int u2mkd_bn_train_forward_from_partial(const float *x, const float *res, int64_
                                         const float *beta, float eps, float momentum, float *running_mean, float *running_var,
                                         int64_t *num_batches_tracked, int32_t relu, const float *partial, int32_t slab_rows,
                                         float *mean /*[c] out*/, float *invstd /*[c] out*/, float *y, u2mkd_stream_t s);
-int u2mkd_bn_eval_forward(const void *x, const void *res, int32_t bf16_rows, int64_t n, int32_t c, const float *gamma,
+int u2mkd_bn_eval_forward(const void *x, const void *res, int32_t row_dtype, int64_t n, int32_t c, const float *gamma,
                           const float *beta, float eps, const float *running_mean, const float *running_var, int32_t relu,
                           float *invstd /*[c] out*/, void *y, u2mkd_stream_t s);
-int u2mkd_bn_backward(const void *dy, const void *x, const void *res, int32_t bf16_rows, int64_t n, int32_t c,
+int u2mkd_bn_backward(const void *dy, const void *x, const void *res, int32_t row_dtype, int64_t n, int32_t c,
                       const float *mean, const float *invstd, const float *gamma, const float *beta, int32_t relu,
                       int32_t training, float *partial, float *dgamma /*[c]*/, float *dbeta /*[c]*/, void *dx, void *dres,
                       u2mkd_stream_t s);
@@ -599,18 +638,18 @@ int u2mkd_bn_backward(const void *dy, const void *x, const void *res, int32_t bf
  * collective between them: local (mean, M2, count) -> all_gather -> merge in rank order (Chan) ->
  * normalise(+ residual, ReLU); backward: local (sum dy', sum dy'*xhat) -> all_reduce -> apply with the global
  * count.  stats rows are [2c+1] = mean[c], M2[c], count.                                        */
-int u2mkd_bn_local_stats(const void *x, int32_t bf16_rows, int64_t n, int32_t c, float *partial /*[slabs,2,c]*/,
+int u2mkd_bn_local_stats(const void *x, int32_t row_dtype, int64_t n, int32_t c, float *partial /*[slabs,2,c]*/,
                          float *stats /*[2c+1]*/, u2mkd_stream_t s);
 int u2mkd_bn_merge_stats(const float *gathered /*[world,2c+1]*/, int32_t world, int32_t c, float eps, float momentum,
                          float *running_mean, float *running_var, float *mean /*[c]*/, float *invstd /*[c]*/,
                          float *total /*[1]*/, int64_t *num_batches_tracked, u2mkd_stream_t s);
-int u2mkd_bn_apply(const void *x, const void *res, int32_t bf16_rows, int64_t n, int32_t c, const float *mean,
+int u2mkd_bn_apply(const void *x, const void *res, int32_t row_dtype, int64_t n, int32_t c, const float *mean,
                    const float *invstd, const float *gamma, const float *beta, int32_t relu, void *y, u2mkd_stream_t s);
-int u2mkd_bn_backward_local(const void *dy, const void *x, const void *res, int32_t bf16_rows, int64_t n, int32_t c,
+int u2mkd_bn_backward_local(const void *dy, const void *x, const void *res, int32_t row_dtype, int64_t n, int32_t c,
                             const float *mean, const float *invstd, const float *gamma, const float *beta, int32_t relu,
                             float *partial /*[slabs,2,c]*/, float *sums /*[2c]: dbeta, dgamma*/, float *keep /*[2c]*/,
                             u2mkd_stream_t s);
-int u2mkd_bn_backward_apply(const void *dy, const void *x, const void *res, int32_t bf16_rows, int64_t n, int32_t c,
+int u2mkd_bn_backward_apply(const void *dy, const void *x, const void *res, int32_t row_dtype, int64_t n, int32_t c,
                             const float *total_n /*[1] device*/, const float *mean, const float *invstd, const float *gamma,
                             const float *beta, int32_t relu, const float *sums /*[2c] over all ranks*/, void *dx, void *dres,
                             u2mkd_stream_t s);

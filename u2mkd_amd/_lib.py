@@ -86,10 +86,15 @@ SIGNATURES = {
     'u2mkd_conv_wgrad_pairs_workspace_bytes': (_sz, [_i64, _i32, _i32, _i32]),
     'u2mkd_conv_wgrad_pairs': (C.c_int, [_p, _i32, _p, _i32, _p, _p, _i64, _i32, _i32, _p, _sz, _p, _p]),
     'u2mkd_conv_forward_tiles_bf16': (C.c_int, [_p, _i64, _i32, _p, _i32, _p, _p, _p, _p, _i64, _i32, _i32, _p, _p]),
+    'u2mkd_conv_forward_tiles_f16': (C.c_int, [_p, _i64, _i32, _p, _i32, _p, _p, _p, _p, _i64, _i32, _i32, _p, _p]),
     'u2mkd_conv_wgrad_pairs_bf16': (C.c_int, [_p, _i32, _p, _i32, _p, _p, _i64, _i32, _i32, _p, _sz, _p, _p]),
+    'u2mkd_conv_wgrad_pairs_f16': (C.c_int, [_p, _i32, _p, _i32, _p, _p, _i64, _i32, _i32, _p, _sz, _p, _p]),
     'u2mkd_conv_forward_pairs_bf16': (C.c_int, [_p, _i64, _i32, _p, _i32, _p, _p, _p, _i64, _i32, _p, _p]),
+    'u2mkd_conv_forward_pairs_f16': (C.c_int, [_p, _i64, _i32, _p, _i32, _p, _p, _p, _i64, _i32, _p, _p]),
     'u2mkd_linear_forward_bf16': (C.c_int, [_p, _i64, _i32, _p, _i32, _p, _p, _p]),
+    'u2mkd_linear_forward_f16': (C.c_int, [_p, _i64, _i32, _p, _i32, _p, _p, _p]),
     'u2mkd_pairs_gather_sum_bf16': (C.c_int, [_p, _p, _i64, _i32, _i32, _p, _p]),
+    'u2mkd_pairs_gather_sum_f16': (C.c_int, [_p, _p, _i64, _i32, _i32, _p, _p]),
     'u2mkd_convolution_workspace_bytes': (_sz, [_i64, _i64, _i32, _i32, _p, _i32]),
     'u2mkd_convolution_forward': (C.c_int, [_p, _i64, _i32, _p, _i64, _i32, _p, _p, _p, _i32, _i32, _p, _sz, _p]),
     'u2mkd_convolution_backward': (C.c_int, [_p, _i64, _i32, _p, _p, _i64, _i32, _p, _p, _p, _p, _i32, _i32, _p, _sz, _p]),
@@ -138,8 +143,11 @@ SIGNATURES = {
     'u2mkd_devoxelize_backward': (C.c_int, [_p, _p, _p, _i64, _i64, _i32, _p, _p]),
     'u2mkd_segment_sum': (C.c_int, [_p, _i32, _p, _p, _p, _i64, _i32, _p, _p]),
     'u2mkd_voxelize_backward_bf16': (C.c_int, [_p, _p, _p, _i64, _i64, _i32, _p, _p]),
+    'u2mkd_voxelize_backward_f16': (C.c_int, [_p, _p, _p, _i64, _i64, _i32, _p, _p]),
     'u2mkd_devoxelize_forward_bf16': (C.c_int, [_p, _p, _p, _i64, _i32, _p, _p]),
+    'u2mkd_devoxelize_forward_f16': (C.c_int, [_p, _p, _p, _i64, _i32, _p, _p]),
     'u2mkd_segment_sum_bf16': (C.c_int, [_p, _i32, _p, _p, _p, _i64, _i32, _p, _p]),
+    'u2mkd_segment_sum_f16': (C.c_int, [_p, _i32, _p, _p, _p, _i64, _i32, _p, _p]),
     'u2mkd_c2l_plan': (C.c_int, [_p, _p, _i32, _i64, _i32, _i32, _i32, _p, _p, _p]),
     'u2mkd_l2c_keys': (C.c_int, [_p, _p, _i32, _i64, _i32, _i64, _i64, _i32, _i32, _p, _p, _p, _p, _p]),
     'u2mkd_l2c_finish': (C.c_int, [_p, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p]),

@@ -23,7 +23,7 @@ namespace u2mkd {
 constexpr int kBnThreads = 256;
 constexpr int kBnSlabRows = 128;   // rows per workgroup in the partial passes (>= 600 workgroups at 80k rows)
 
-// Rows are float or bf16 (common.h: bf16row, ld4, st4).  BF16 STORAGE (BASELINE.json configs[4]): under autocast the
+// Rows are float, bf16 or fp16 (common.h: bf16row, _Float16, ld4, st4; the entries' row-dtype argument 0 / 1 / 2).  BF16 STORAGE (BASELINE.json configs[4]): under autocast the
 // reference's BatchNorm1d takes and returns half rows with fp32 statistics; here bf16 rows, every sum, mean, invstd
 // and gradient sum in fp32, one rounding per stored element.
 // thread layout for a [rows, C4 float4] slab: j = float4 column, ry = row lane
@@ -503,7 +503,7 @@ static size_t bn_lds_bytes(int c, int arrays) {
     return (size_t)arrays * rl * cw * sizeof(float4);
 }
 
-// ---- launch sequences, shared by the fp32-row and the bf16-row entry points ------------------------------------
+// ---- launch sequences, shared by the fp32-, bf16- and fp16-row entry points ------------------------------------
 // U2MKD_BN_STATS_SERIAL=1: the statistics pass in its two-read form for every width (A/B; the partials are bitwise the same)
 static bool bn_stats_serial() {
     static const bool on = [] { const char *e = getenv("U2MKD_BN_STATS_SERIAL"); return e && e[0] == '1'; }();
@@ -671,6 +671,10 @@ using namespace u2mkd;
 // the row pointers of the entries below as the rows of one dtype
 #define BF(p) reinterpret_cast<const bf16row *>(p)
 #define BFW(p) reinterpret_cast<bf16row *>(p)
+#define H16(p) reinterpret_cast<const _Float16 *>(p)
+#define H16W(p) reinterpret_cast<_Float16 *>(p)
+// the row-dtype argument: 0 = fp32, 1 = bf16, 2 = fp16; anything else is an error
+#define U2_ROW_DTYPE(who) U2_REQUIRE(row_dtype >= 0 && row_dtype <= 2, who ": row dtype %d must be 0 (fp32), 1 (bf16) or 2 (fp16)", row_dtype)
 #define F32(p) reinterpret_cast<const float *>(p)
 #define F32W(p) reinterpret_cast<float *>(p)
 
@@ -678,11 +682,15 @@ extern "C" {
 
 int64_t u2mkd_bn_num_slabs(int64_t n) { return n > 0 ? (n + kBnSlabRows - 1) / kBnSlabRows : 0; }
 
-int u2mkd_bn_train_forward(const void *x, const void *res, int32_t bf16_rows, int64_t n, int32_t c, const float *gamma,
+int u2mkd_bn_train_forward(const void *x, const void *res, int32_t row_dtype, int64_t n, int32_t c, const float *gamma,
                            const float *beta, float eps, float momentum, float *running_mean, float *running_var,
                            int64_t *num_batches_tracked, int32_t relu, float *partial, float *mean, float *invstd, void *y,
                            u2mkd_stream_t s) {
-    if (bf16_rows)
+    U2_ROW_DTYPE("u2mkd_bn_train_forward");
+    if (row_dtype == 2)
+        return bn_train_forward_impl<_Float16>(H16(x), H16(res), n, c, gamma, beta, eps, momentum, running_mean, running_var,
+                                              num_batches_tracked, relu, partial, mean, invstd, H16W(y), s);
+    if (row_dtype == 1)
         return bn_train_forward_impl<bf16row>(BF(x), BF(res), n, c, gamma, beta, eps, momentum, running_mean, running_var,
                                               num_batches_tracked, relu, partial, mean, invstd, BFW(y), s);
     return bn_train_forward_impl<float>(F32(x), F32(res), n, c, gamma, beta, eps, momentum, running_mean, running_var,
@@ -697,20 +705,28 @@ int u2mkd_bn_train_forward_from_partial(const float *x, const float *res, int64_
                                               num_batches_tracked, relu, partial, slab_rows, mean, invstd, y, s);
 }
 
-int u2mkd_bn_eval_forward(const void *x, const void *res, int32_t bf16_rows, int64_t n, int32_t c, const float *gamma,
+int u2mkd_bn_eval_forward(const void *x, const void *res, int32_t row_dtype, int64_t n, int32_t c, const float *gamma,
                           const float *beta, float eps, const float *running_mean, const float *running_var, int32_t relu,
                           float *invstd, void *y, u2mkd_stream_t s) {
-    if (bf16_rows)
+    U2_ROW_DTYPE("u2mkd_bn_eval_forward");
+    if (row_dtype == 2)
+        return bn_eval_forward_impl<_Float16>(H16(x), H16(res), n, c, gamma, beta, eps, running_mean, running_var, relu, invstd,
+                                             H16W(y), s);
+    if (row_dtype == 1)
         return bn_eval_forward_impl<bf16row>(BF(x), BF(res), n, c, gamma, beta, eps, running_mean, running_var, relu, invstd,
                                              BFW(y), s);
     return bn_eval_forward_impl<float>(F32(x), F32(res), n, c, gamma, beta, eps, running_mean, running_var, relu, invstd,
                                        F32W(y), s);
 }
 
-int u2mkd_bn_backward(const void *dy, const void *x, const void *res, int32_t bf16_rows, int64_t n, int32_t c,
+int u2mkd_bn_backward(const void *dy, const void *x, const void *res, int32_t row_dtype, int64_t n, int32_t c,
                       const float *mean, const float *invstd, const float *gamma, const float *beta, int32_t relu,
                       int32_t training, float *partial, float *dgamma, float *dbeta, void *dx, void *dres, u2mkd_stream_t s) {
-    if (bf16_rows)
+    U2_ROW_DTYPE("u2mkd_bn_backward");
+    if (row_dtype == 2)
+        return bn_backward_impl<_Float16>(H16(dy), H16(x), H16(res), n, c, mean, invstd, gamma, beta, relu, training, partial,
+                                         dgamma, dbeta, H16W(dx), H16W(dres), s);
+    if (row_dtype == 1)
         return bn_backward_impl<bf16row>(BF(dy), BF(x), BF(res), n, c, mean, invstd, gamma, beta, relu, training, partial,
                                          dgamma, dbeta, BFW(dx), BFW(dres), s);
     return bn_backward_impl<float>(F32(dy), F32(x), F32(res), n, c, mean, invstd, gamma, beta, relu, training, partial, dgamma,
@@ -719,9 +735,11 @@ int u2mkd_bn_backward(const void *dy, const void *x, const void *res, int32_t bf
 
 /* ---- SyncBatchNorm pieces: local statistics | (all_gather by the caller) | merge | apply, and
  * local sums | (all_reduce by the caller) | apply in the backward ---- */
-int u2mkd_bn_local_stats(const void *x, int32_t bf16_rows, int64_t n, int32_t c, float *partial, float *stats,
+int u2mkd_bn_local_stats(const void *x, int32_t row_dtype, int64_t n, int32_t c, float *partial, float *stats,
                          u2mkd_stream_t s) {
-    if (bf16_rows) return bn_local_stats_impl<bf16row>(BF(x), n, c, partial, stats, s);
+    U2_ROW_DTYPE("u2mkd_bn_local_stats");
+    if (row_dtype == 2) return bn_local_stats_impl<_Float16>(H16(x), n, c, partial, stats, s);
+    if (row_dtype == 1) return bn_local_stats_impl<bf16row>(BF(x), n, c, partial, stats, s);
     return bn_local_stats_impl<float>(F32(x), n, c, partial, stats, s);
 }
 
@@ -734,26 +752,36 @@ int u2mkd_bn_merge_stats(const float *gathered, int32_t world, int32_t c, float 
     return check_launch("u2mkd_bn_merge_stats");
 }
 
-int u2mkd_bn_apply(const void *x, const void *res, int32_t bf16_rows, int64_t n, int32_t c, const float *mean,
+int u2mkd_bn_apply(const void *x, const void *res, int32_t row_dtype, int64_t n, int32_t c, const float *mean,
                    const float *invstd, const float *gamma, const float *beta, int32_t relu, void *y, u2mkd_stream_t s) {
-    if (bf16_rows) return bn_apply_impl<bf16row>(BF(x), BF(res), n, c, mean, invstd, gamma, beta, relu, BFW(y), s);
+    U2_ROW_DTYPE("u2mkd_bn_apply");
+    if (row_dtype == 2) return bn_apply_impl<_Float16>(H16(x), H16(res), n, c, mean, invstd, gamma, beta, relu, H16W(y), s);
+    if (row_dtype == 1) return bn_apply_impl<bf16row>(BF(x), BF(res), n, c, mean, invstd, gamma, beta, relu, BFW(y), s);
     return bn_apply_impl<float>(F32(x), F32(res), n, c, mean, invstd, gamma, beta, relu, F32W(y), s);
 }
 
-int u2mkd_bn_backward_local(const void *dy, const void *x, const void *res, int32_t bf16_rows, int64_t n, int32_t c,
+int u2mkd_bn_backward_local(const void *dy, const void *x, const void *res, int32_t row_dtype, int64_t n, int32_t c,
                             const float *mean, const float *invstd, const float *gamma, const float *beta, int32_t relu,
                             float *partial, float *sums, float *keep, u2mkd_stream_t s) {
-    if (bf16_rows)
+    U2_ROW_DTYPE("u2mkd_bn_backward_local");
+    if (row_dtype == 2)
+        return bn_backward_local_impl<_Float16>(H16(dy), H16(x), H16(res), n, c, mean, invstd, gamma, beta, relu, partial, sums,
+                                               keep, s);
+    if (row_dtype == 1)
         return bn_backward_local_impl<bf16row>(BF(dy), BF(x), BF(res), n, c, mean, invstd, gamma, beta, relu, partial, sums,
                                                keep, s);
     return bn_backward_local_impl<float>(F32(dy), F32(x), F32(res), n, c, mean, invstd, gamma, beta, relu, partial, sums, keep,
                                          s);
 }
 
-int u2mkd_bn_backward_apply(const void *dy, const void *x, const void *res, int32_t bf16_rows, int64_t n, int32_t c,
+int u2mkd_bn_backward_apply(const void *dy, const void *x, const void *res, int32_t row_dtype, int64_t n, int32_t c,
                             const float *total_n, const float *mean, const float *invstd, const float *gamma,
                             const float *beta, int32_t relu, const float *sums, void *dx, void *dres, u2mkd_stream_t s) {
-    if (bf16_rows)
+    U2_ROW_DTYPE("u2mkd_bn_backward_apply");
+    if (row_dtype == 2)
+        return bn_backward_apply_impl<_Float16>(H16(dy), H16(x), H16(res), n, c, total_n, mean, invstd, gamma, beta, relu, sums,
+                                               H16W(dx), H16W(dres), s);
+    if (row_dtype == 1)
         return bn_backward_apply_impl<bf16row>(BF(dy), BF(x), BF(res), n, c, total_n, mean, invstd, gamma, beta, relu, sums,
                                                BFW(dx), BFW(dres), s);
     return bn_backward_apply_impl<float>(F32(dy), F32(x), F32(res), n, c, total_n, mean, invstd, gamma, beta, relu, sums,

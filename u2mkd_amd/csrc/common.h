@@ -44,16 +44,23 @@ __device__ __forceinline__ int64_t fnv_hash4(int x, int y, int z, int b) {
     return (int64_t)h;
 }
 
-// ---- feature-row element types: float, or bf16 (BF16 STORAGE, BASELINE.json configs[4]) --------------------------
-// ld4 / st4 move 4 consecutive channels of a row (index in units of 4 elements); bf16 values are widened exactly on
-// load and rounded to nearest-even once at the store, arithmetic in between is fp32.
+// ---- feature-row element types: float, bf16 (BF16 STORAGE, BASELINE.json configs[4]) or fp16 (_Float16: FP16 STORAGE, the
+// reference's amp mode) ----
+// ld4 / st4 move 4 consecutive channels of a row (index in units of 4 elements); 16-bit values are widened exactly on
+// load and rounded to nearest-even once at the store, arithmetic in between is fp32.  An fp32 value beyond fp16's range is
+// stored as +-inf (never saturated: GradScaler finds an overflowed step by its non-finite gradients), NaN stays NaN.
 struct bf16row { unsigned short v; };
+typedef _Float16 u2_f16row4 __attribute__((ext_vector_type(4)));
 template <typename T> __device__ __forceinline__ float4 ld4(const T *p, int64_t i4);
 template <> __device__ __forceinline__ float4 ld4<float>(const float *p, int64_t i4) { return reinterpret_cast<const float4 *>(p)[i4]; }
 template <> __device__ __forceinline__ float4 ld4<bf16row>(const bf16row *p, int64_t i4) {
     const uint2 w = reinterpret_cast<const uint2 *>(p)[i4];     // a bf16 is the upper half of the fp32 with the same value
     return make_float4(__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xffff0000u), __uint_as_float(w.y << 16),
                        __uint_as_float(w.y & 0xffff0000u));
+}
+template <> __device__ __forceinline__ float4 ld4<_Float16>(const _Float16 *p, int64_t i4) {
+    const u2_f16row4 h = reinterpret_cast<const u2_f16row4 *>(p)[i4];
+    return make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
 }
 template <typename T> __device__ __forceinline__ void st4(T *p, int64_t i4, const float4 &v);
 template <> __device__ __forceinline__ void st4<float>(float *p, int64_t i4, const float4 &v) { reinterpret_cast<float4 *>(p)[i4] = v; }
@@ -63,6 +70,10 @@ template <> __device__ __forceinline__ void st4<bf16row>(bf16row *p, int64_t i4,
     w.x = (uint32_t)__builtin_bit_cast(unsigned short, a) | ((uint32_t)__builtin_bit_cast(unsigned short, b) << 16);
     w.y = (uint32_t)__builtin_bit_cast(unsigned short, c) | ((uint32_t)__builtin_bit_cast(unsigned short, d) << 16);
     reinterpret_cast<uint2 *>(p)[i4] = w;
+}
+template <> __device__ __forceinline__ void st4<_Float16>(_Float16 *p, int64_t i4, const float4 &v) {
+    const u2_f16row4 h = {(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};      // round to nearest even, overflow -> inf
+    reinterpret_cast<u2_f16row4 *>(p)[i4] = h;
 }
 
 

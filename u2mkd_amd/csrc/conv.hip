@@ -424,6 +424,12 @@ __device__ __forceinline__ f32x4 widen_bf16x4(const char *p) {
     return v;
 }
 
+// 4 fp16 channels (8 bytes) -> f32x4, exactly
+__device__ __forceinline__ f32x4 widen_f16x4(const char *p) {
+    const u2_h16x4 h = *reinterpret_cast<const u2_h16x4 *>(p);
+    return (f32x4){(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
+}
+
 __global__ void wgrad_plan_kernel(const int32_t *__restrict__ nbsizes, int K, int g_target, int cp,
                                   int32_t *__restrict__ plan) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -441,8 +447,8 @@ __global__ void wgrad_plan_kernel(const int32_t *__restrict__ nbsizes, int K, in
 }
 
 // B16: a and b are BF16 rows (bf16 storage, BASELINE.json configs[4]): 8-byte gathers of 4 channels, widened to fp32
-// in registers; LDS images, MFMA arithmetic (f32) and slabs as in the fp32 form.
-template <int WM, int WN, int CP, bool STAMP = false, bool B16 = false>
+// in registers; LDS images, MFMA arithmetic (f32) and slabs as in the fp32 form.  H16 (with B16): the 2-byte rows are fp16.
+template <int WM, int WN, int CP, bool STAMP = false, bool B16 = false, bool H16 = false>
 __global__ void __launch_bounds__(256)
 conv_wgrad_pairs_kernel(const float *__restrict__ a, int ca, const float *__restrict__ b, int cb,
                         const int32_t *__restrict__ pairs, const int32_t *__restrict__ plan, int K, int swap,
@@ -530,13 +536,15 @@ conv_wgrad_pairs_kernel(const float *__restrict__ a, int ca, const float *__rest
 #pragma unroll
         for (int i = 0; i < PA; ++i) {
             const int c = min(a0 + ((tid + 256 * i) % FA) * 4, ca_ok);
-            if (B16) va[i] = widen_bf16x4(reinterpret_cast<const char *>(a) + ((size_t)xa[i] * ca + c) * 2);
+            if (H16) va[i] = widen_f16x4(reinterpret_cast<const char *>(a) + ((size_t)xa[i] * ca + c) * 2);
+            else if (B16) va[i] = widen_bf16x4(reinterpret_cast<const char *>(a) + ((size_t)xa[i] * ca + c) * 2);
             else va[i] = *reinterpret_cast<const f32x4 *>(a + (size_t)xa[i] * ca + c);
         }
 #pragma unroll
         for (int i = 0; i < PB; ++i) {
             const int c = min(b0 + ((tid + 256 * i) % FB) * 4, cb_ok);
-            if (B16) vb[i] = widen_bf16x4(reinterpret_cast<const char *>(b) + ((size_t)xb[i] * cb + c) * 2);
+            if (H16) vb[i] = widen_f16x4(reinterpret_cast<const char *>(b) + ((size_t)xb[i] * cb + c) * 2);
+            else if (B16) vb[i] = widen_bf16x4(reinterpret_cast<const char *>(b) + ((size_t)xb[i] * cb + c) * 2);
             else vb[i] = *reinterpret_cast<const f32x4 *>(b + (size_t)xb[i] * cb + c);
         }
     };
@@ -981,10 +989,11 @@ pairs_gather_sum_stats_kernel(const float *__restrict__ y, const int32_t *__rest
 }
 
 // the same over bf16 rows (bf16 storage, BASELINE.json configs[4]): 8 channels = 16 bytes per thread, fp32 sum in ascending
-// offset order, one rounding to bf16 at the store
+// offset order, one rounding to bf16 at the store.  H16: the rows are fp16 (fp16 storage; a sum beyond fp16's range: +-inf)
+template <bool H16>
 __global__ void __launch_bounds__(256)
-pairs_gather_sum_bf16_kernel(const uint4 *__restrict__ y, const int32_t *__restrict__ pos, int64_t n_rows, int K, int c8,
-                             uint4 *__restrict__ out) {
+pairs_gather_sum_rows16_kernel(const uint4 *__restrict__ y, const int32_t *__restrict__ pos, int64_t n_rows, int K, int c8,
+                               uint4 *__restrict__ out) {
     int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= n_rows * c8) return;
     int64_t r = t / c8;
@@ -1004,18 +1013,17 @@ pairs_gather_sum_bf16_kernel(const uint4 *__restrict__ y, const int32_t *__restr
         for (int i = 0; i < 8; ++i) {
             const uint32_t w[4] = {v[i].x, v[i].y, v[i].z, v[i].w};
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {      // a bf16 is the upper half of the fp32 with the same value
-                acc[2 * j] += __uint_as_float(w[j] << 16);
-                acc[2 * j + 1] += __uint_as_float(w[j] & 0xffff0000u);
+            for (int j = 0; j < 4; ++j) {
+                float lo, hi;
+                unpack_rows16<H16>(w[j], lo, hi);
+                acc[2 * j] += lo;
+                acc[2 * j + 1] += hi;
             }
         }
     }
     uint32_t o[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const __bf16 lo = (__bf16)acc[2 * j], hi = (__bf16)acc[2 * j + 1];
-        o[j] = (uint32_t)__builtin_bit_cast(unsigned short, lo) | ((uint32_t)__builtin_bit_cast(unsigned short, hi) << 16);
-    }
+    for (int j = 0; j < 4; ++j) o[j] = pack_rows16<H16>(acc[2 * j], acc[2 * j + 1]);
     out[r * c8 + c] = make_uint4(o[0], o[1], o[2], o[3]);
 }
 
@@ -1177,7 +1185,7 @@ size_t u2mkd_weight_fragments_bytes(int32_t k, int32_t rows, int32_t cols, int32
 int u2mkd_weight_fragments(const float *w, int32_t k, int32_t rows, int32_t cols, int32_t transpose, int32_t arith,
                            void *wf, u2mkd_stream_t s) {
     U2_REQUIRE(w && wf, "u2mkd_weight_fragments: null pointer");
-    U2_REQUIRE(arith >= 0 && arith <= 4, "u2mkd_weight_fragments: arith must be 0 (default), 1 (f32), 2 (bf16x3), 3 (bf16 storage) or 4 (f16x2)");
+    U2_REQUIRE(arith >= 0 && arith <= 5, "u2mkd_weight_fragments: arith must be 0 (default), 1 (f32), 2 (bf16x3), 3 (bf16 storage), 4 (f16x2) or 5 (fp16 storage)");
     U2_REQUIRE(k > 0 && rows > 0 && cols > 0 && rows % 32 == 0 && cols % 32 == 0,
                "u2mkd_weight_fragments: [%d, %d, %d]: rows and cols must be positive multiples of 32", k, rows, cols);
     U2_REQUIRE(transpose >= 0 && transpose <= 2, "u2mkd_weight_fragments: transpose must be 0, 1 or 2 (both)");
@@ -1383,40 +1391,78 @@ int u2mkd_pairs_gather_sum_ep(const float *y, const int32_t *pos, int64_t n_rows
     return check_launch("u2mkd_pairs_gather_sum_ep");
 }
 
+/* ---- 16-bit storage rows: one implementation per entry pair, `rows16` = Row16 of the rows, `who` = the entry's name ---- */
+static int conv_forward_pairs_rows16(const char *who, int rows16, const void *in, int64_t n_in, int32_t cin, const void *wf,
+                                     int32_t cout, const int32_t *pair_idx, const int32_t *tile_k, const int32_t *meta,
+                                     int64_t capacity, int32_t k, void *y, u2mkd_stream_t s) {
+    if (capacity == 0) return 0;
+    U2_REQUIRE(in && wf && pair_idx && tile_k && meta && y, "%s: null pointer", who);
+    U2_REQUIRE(k > 0 && n_in > 0 && capacity % 64 == 0, "%s: the capacity must be a multiple of 64", who);
+    int rc = launch_conv_px3(who, reinterpret_cast<const float *>(in), cin, reinterpret_cast<const float *>(wf), cout, pair_idx,
+                             tile_k, meta + 1, capacity, reinterpret_cast<float *>(y), as_stream(s), rows16);
+    U2_REQUIRE(rc >= 0, "%s: cin=%d and cout=%d must be multiples of 32", who, cin, cout);
+    return rc;
+}
+
+static int linear_forward_rows16(const char *who, int rows16, const void *x, int64_t n, int32_t cin, const void *wf,
+                                 int32_t cout, const float *bias, void *y, u2mkd_stream_t s) {
+    if (n == 0) return 0;
+    U2_REQUIRE(x && wf && y, "%s: null pointer", who);
+    U2_REQUIRE(n > 0 && n < ((int64_t)1 << 31) - 64, "%s: %lld rows out of range", who, (long long)n);
+    int rc = launch_linear_px3(who, reinterpret_cast<const float *>(x), n, cin, reinterpret_cast<const float *>(wf), cout, bias,
+                               reinterpret_cast<float *>(y), as_stream(s), rows16);
+    U2_REQUIRE(rc >= 0, "%s: cin=%d and cout=%d must be multiples of 32", who, cin, cout);
+    return rc;
+}
+
+static int pairs_gather_sum_rows16(const char *who, int rows16, const void *y, const int32_t *pos, int64_t n_rows, int32_t k,
+                                   int32_t cout, void *out, u2mkd_stream_t s) {
+    if (n_rows == 0) return 0;
+    U2_REQUIRE(y && pos && out, "%s: null pointer", who);
+    U2_REQUIRE(cout > 0 && cout % 8 == 0 && k > 0, "%s: cout=%d must be a positive multiple of 8", who, cout);
+    const int c8 = cout / 8;
+    const int64_t total = n_rows * c8;
+    if (rows16 == kRowsF16)
+        hipLaunchKernelGGL(pairs_gather_sum_rows16_kernel<true>, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, as_stream(s),
+                           reinterpret_cast<const uint4 *>(y), pos, n_rows, k, c8, reinterpret_cast<uint4 *>(out));
+    else
+        hipLaunchKernelGGL(pairs_gather_sum_rows16_kernel<false>, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, as_stream(s),
+                           reinterpret_cast<const uint4 *>(y), pos, n_rows, k, c8, reinterpret_cast<uint4 *>(out));
+    return check_launch(who);
+}
+
 int u2mkd_conv_forward_pairs_bf16(const void *in, int64_t n_in, int32_t cin, const void *wf, int32_t cout,
                                    const int32_t *pair_idx, const int32_t *tile_k, const int32_t *meta, int64_t capacity,
                                    int32_t k, void *y, u2mkd_stream_t s) {
-    if (capacity == 0) return 0;
-    U2_REQUIRE(in && wf && pair_idx && tile_k && meta && y, "u2mkd_conv_forward_pairs_bf16: null pointer");
-    U2_REQUIRE(k > 0 && n_in > 0 && capacity % 64 == 0, "u2mkd_conv_forward_pairs_bf16: the capacity must be a multiple of 64");
-    int rc = launch_conv_px3("u2mkd_conv_forward_pairs_bf16", reinterpret_cast<const float *>(in), cin,
-                             reinterpret_cast<const float *>(wf), cout, pair_idx, tile_k, meta + 1, capacity,
-                             reinterpret_cast<float *>(y), as_stream(s), true);
-    U2_REQUIRE(rc >= 0, "u2mkd_conv_forward_pairs_bf16: cin=%d and cout=%d must be multiples of 32", cin, cout);
-    return rc;
+    return conv_forward_pairs_rows16("u2mkd_conv_forward_pairs_bf16", kRowsBf16, in, n_in, cin, wf, cout, pair_idx, tile_k, meta,
+                                     capacity, k, y, s);
+}
+
+int u2mkd_conv_forward_pairs_f16(const void *in, int64_t n_in, int32_t cin, const void *wf, int32_t cout,
+                                  const int32_t *pair_idx, const int32_t *tile_k, const int32_t *meta, int64_t capacity,
+                                  int32_t k, void *y, u2mkd_stream_t s) {
+    return conv_forward_pairs_rows16("u2mkd_conv_forward_pairs_f16", kRowsF16, in, n_in, cin, wf, cout, pair_idx, tile_k, meta,
+                                     capacity, k, y, s);
 }
 
 int u2mkd_linear_forward_bf16(const void *x, int64_t n, int32_t cin, const void *wf, int32_t cout, const float *bias,
                               void *y, u2mkd_stream_t s) {
-    if (n == 0) return 0;
-    U2_REQUIRE(x && wf && y, "u2mkd_linear_forward_bf16: null pointer");
-    U2_REQUIRE(n > 0 && n < ((int64_t)1 << 31) - 64, "u2mkd_linear_forward_bf16: %lld rows out of range", (long long)n);
-    int rc = launch_linear_px3("u2mkd_linear_forward_bf16", reinterpret_cast<const float *>(x), n, cin,
-                               reinterpret_cast<const float *>(wf), cout, bias, reinterpret_cast<float *>(y), as_stream(s), true);
-    U2_REQUIRE(rc >= 0, "u2mkd_linear_forward_bf16: cin=%d and cout=%d must be multiples of 32", cin, cout);
-    return rc;
+    return linear_forward_rows16("u2mkd_linear_forward_bf16", kRowsBf16, x, n, cin, wf, cout, bias, y, s);
+}
+
+int u2mkd_linear_forward_f16(const void *x, int64_t n, int32_t cin, const void *wf, int32_t cout, const float *bias,
+                             void *y, u2mkd_stream_t s) {
+    return linear_forward_rows16("u2mkd_linear_forward_f16", kRowsF16, x, n, cin, wf, cout, bias, y, s);
 }
 
 int u2mkd_pairs_gather_sum_bf16(const void *y, const int32_t *pos, int64_t n_rows, int32_t k, int32_t cout, void *out,
                                 u2mkd_stream_t s) {
-    if (n_rows == 0) return 0;
-    U2_REQUIRE(y && pos && out, "u2mkd_pairs_gather_sum_bf16: null pointer");
-    U2_REQUIRE(cout > 0 && cout % 8 == 0 && k > 0, "u2mkd_pairs_gather_sum_bf16: cout=%d must be a positive multiple of 8", cout);
-    const int c8 = cout / 8;
-    const int64_t total = n_rows * c8;
-    hipLaunchKernelGGL(pairs_gather_sum_bf16_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, as_stream(s),
-                       reinterpret_cast<const uint4 *>(y), pos, n_rows, k, c8, reinterpret_cast<uint4 *>(out));
-    return check_launch("u2mkd_pairs_gather_sum_bf16");
+    return pairs_gather_sum_rows16("u2mkd_pairs_gather_sum_bf16", kRowsBf16, y, pos, n_rows, k, cout, out, s);
+}
+
+int u2mkd_pairs_gather_sum_f16(const void *y, const int32_t *pos, int64_t n_rows, int32_t k, int32_t cout, void *out,
+                               u2mkd_stream_t s) {
+    return pairs_gather_sum_rows16("u2mkd_pairs_gather_sum_f16", kRowsF16, y, pos, n_rows, k, cout, out, s);
 }
 
 int u2mkd_debug_wgrad_stamps(const float *a, const float *b, const int32_t *pairs, const int32_t *plan, int64_t n_rows,
@@ -1444,7 +1490,7 @@ size_t u2mkd_conv_wgrad_pairs_workspace_bytes(int64_t n_rows, int32_t ca, int32_
     return ((size_t)wgrad_g_target(n_rows, k) + k) * (size_t)ca * cb * sizeof(float);
 }
 
-static int wgrad_pairs_impl(bool b16, const float *a, int32_t ca, const float *b, int32_t cb, const int32_t *pairs,
+static int wgrad_pairs_impl(int rows16 /* Row16 of a and b */, const float *a, int32_t ca, const float *b, int32_t cb, const int32_t *pairs,
                             const int32_t *plan, int64_t n_rows, int32_t k, int32_t swap, void *workspace,
                             size_t workspace_bytes, float *dw, u2mkd_stream_t s) {
     U2_REQUIRE(dw, "u2mkd_conv_wgrad_pairs: null pointer");
@@ -1461,10 +1507,11 @@ static int wgrad_pairs_impl(bool b16, const float *a, int32_t ca, const float *b
     hipStream_t st = as_stream(s);
     // bf16x3 form (conv_wgrad_x3.hip, 64 x 64-channel tiles) for every shape whose channel counts are multiples of 64
     const bool x3_shape = ca % 64 == 0 && cb % 64 == 0;
+    const bool b16 = rows16 != kRowsF32;
     if (x3_shape && (b16 || conv_tp_arith(0) == 2) && conv_wgrad_x3_supported(ca, cb, k)) {
-        // (bf16 rows: the same kernel without the split -- one plane, one MFMA per product)
+        // (bf16 / fp16 rows: the same kernel without the split -- one plane, one K = 32 product of the row type)
         const int merge = conv_wgrad_x3_merge(ca, cb);
-        int rc = launch_conv_wgrad_x3(a, ca, b, cb, pairs, plan, k, swap, g, merge, reinterpret_cast<float *>(workspace), st, b16);
+        int rc = launch_conv_wgrad_x3(a, ca, b, cb, pairs, plan, k, swap, g, merge, reinterpret_cast<float *>(workspace), st, rows16);
         if (rc) return rc;
         const int64_t te = (int64_t)ca * cb;
         hipLaunchKernelGGL(wgrad_pairs_reduce_kernel, dim3((unsigned)ceil_div(te, 64), k), dim3(256), 0, st,
@@ -1490,7 +1537,13 @@ static int wgrad_pairs_impl(bool b16, const float *a, int32_t ca, const float *b
         if (lds > 65536)                                                                                            \
             (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_wgrad_pairs_kernel<WM_, WN_, CP_>),      \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                        \
-        if (b16) {                                                                                                  \
+        if (rows16 == kRowsF16) {                                                                                   \
+            if (lds > 65536)                                                                                        \
+                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_wgrad_pairs_kernel<WM_, WN_, CP_, false, true, true>), \
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                    \
+            hipLaunchKernelGGL((conv_wgrad_pairs_kernel<WM_, WN_, CP_, false, true, true>), grid, dim3(256), lds, st, a, ca, b, cb, \
+                               pairs, plan, k, swap, tiles_b, slabs);                                               \
+        } else if (b16) {                                                                                           \
             if (lds > 65536)                                                                                        \
                 (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_wgrad_pairs_kernel<WM_, WN_, CP_, false, true>), \
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                    \
@@ -1528,32 +1581,55 @@ static int wgrad_pairs_impl(bool b16, const float *a, int32_t ca, const float *b
 int u2mkd_conv_wgrad_pairs(const float *a, int32_t ca, const float *b, int32_t cb, const int32_t *pairs,
                            const int32_t *plan, int64_t n_rows, int32_t k, int32_t swap, void *workspace,
                            size_t workspace_bytes, float *dw, u2mkd_stream_t s) {
-    return wgrad_pairs_impl(false, a, ca, b, cb, pairs, plan, n_rows, k, swap, workspace, workspace_bytes, dw, s);
+    return wgrad_pairs_impl(kRowsF32, a, ca, b, cb, pairs, plan, n_rows, k, swap, workspace, workspace_bytes, dw, s);
 }
 
 int u2mkd_conv_wgrad_pairs_bf16(const void *a, int32_t ca, const void *b, int32_t cb, const int32_t *pairs,
                                 const int32_t *plan, int64_t n_rows, int32_t k, int32_t swap, void *workspace,
                                 size_t workspace_bytes, float *dw, u2mkd_stream_t s) {
-    return wgrad_pairs_impl(true, reinterpret_cast<const float *>(a), ca, reinterpret_cast<const float *>(b), cb, pairs, plan,
+    return wgrad_pairs_impl(kRowsBf16, reinterpret_cast<const float *>(a), ca, reinterpret_cast<const float *>(b), cb, pairs, plan,
                             n_rows, k, swap, workspace, workspace_bytes, dw, s);
+}
+
+int u2mkd_conv_wgrad_pairs_f16(const void *a, int32_t ca, const void *b, int32_t cb, const int32_t *pairs,
+                               const int32_t *plan, int64_t n_rows, int32_t k, int32_t swap, void *workspace,
+                               size_t workspace_bytes, float *dw, u2mkd_stream_t s) {
+    return wgrad_pairs_impl(kRowsF16, reinterpret_cast<const float *>(a), ca, reinterpret_cast<const float *>(b), cb, pairs, plan,
+                            n_rows, k, swap, workspace, workspace_bytes, dw, s);
+}
+
+static int conv_forward_tiles_rows16(const char *who, int arith, const void *in, int64_t n_in, int32_t cin, const void *wf,
+                                     int32_t cout, const int32_t *nbr_sorted, const int32_t *order, const int32_t *items,
+                                     const int32_t *n_items, int64_t n_out, int32_t k, int32_t kflip, void *out,
+                                     u2mkd_stream_t s) {
+    if (n_out <= 0) return 0;
+    U2_REQUIRE(in && wf && nbr_sorted && out, "%s: null pointer", who);
+    U2_REQUIRE(kflip == 0 || kflip == 1, "%s: kflip must be 0 or 1", who);
+    U2_REQUIRE(n_in > 0, "%s: empty input", who);
+    U2_REQUIRE(n_in <= (1 << 25), "%s: %lld input rows, the tile kernel packs row indices into 25 bits", who, (long long)n_in);
+    U2_REQUIRE((items == nullptr) == (n_items == nullptr), "%s: items and n_items go together", who);
+    int rc = launch_conv_tp(who, reinterpret_cast<const float *>(in), cin, reinterpret_cast<const float *>(wf), cout, nbr_sorted,
+                            order, RowRange{n_out, 0, n_out, nullptr}, items, n_items, k, kflip, arith,
+                            reinterpret_cast<float *>(out), as_stream(s));
+    U2_REQUIRE(rc >= 0, "%s: no instantiation for %d -> %d channels, kernel volume %d (ask u2mkd_conv_tiles_supported first)",
+               who, cin, cout, k);
+    return rc;
 }
 
 int u2mkd_conv_forward_tiles_bf16(const void *in, int64_t n_in, int32_t cin, const void *wf, int32_t cout,
                                   const int32_t *nbr_sorted, const int32_t *order, const int32_t *items,
                                   const int32_t *n_items, int64_t n_out, int32_t k, int32_t kflip, void *out,
                                   u2mkd_stream_t s) {
-    if (n_out <= 0) return 0;
-    U2_REQUIRE(in && wf && nbr_sorted && out, "u2mkd_conv_forward_tiles_bf16: null pointer");
-    U2_REQUIRE(kflip == 0 || kflip == 1, "u2mkd_conv_forward_tiles_bf16: kflip must be 0 or 1");
-    U2_REQUIRE(n_in > 0, "u2mkd_conv_forward_tiles_bf16: empty input");
-    U2_REQUIRE(n_in <= (1 << 25), "u2mkd_conv_forward_tiles_bf16: %lld input rows, the tile kernel packs row indices into 25 bits", (long long)n_in);
-    U2_REQUIRE((items == nullptr) == (n_items == nullptr), "u2mkd_conv_forward_tiles_bf16: items and n_items go together");
-    int rc = launch_conv_tp("u2mkd_conv_forward_tiles_bf16", reinterpret_cast<const float *>(in), cin,
-                            reinterpret_cast<const float *>(wf), cout, nbr_sorted, order, RowRange{n_out, 0, n_out, nullptr},
-                            items, n_items, k, kflip, 3, reinterpret_cast<float *>(out), as_stream(s));
-    U2_REQUIRE(rc >= 0, "u2mkd_conv_forward_tiles_bf16: no instantiation for %d -> %d channels, kernel volume %d "
-               "(ask u2mkd_conv_tiles_supported first)", cin, cout, k);
-    return rc;
+    return conv_forward_tiles_rows16("u2mkd_conv_forward_tiles_bf16", 3, in, n_in, cin, wf, cout, nbr_sorted, order, items, n_items,
+                                     n_out, k, kflip, out, s);
+}
+
+int u2mkd_conv_forward_tiles_f16(const void *in, int64_t n_in, int32_t cin, const void *wf, int32_t cout,
+                                 const int32_t *nbr_sorted, const int32_t *order, const int32_t *items,
+                                 const int32_t *n_items, int64_t n_out, int32_t k, int32_t kflip, void *out,
+                                 u2mkd_stream_t s) {
+    return conv_forward_tiles_rows16("u2mkd_conv_forward_tiles_f16", 5, in, n_in, cin, wf, cout, nbr_sorted, order, items, n_items,
+                                     n_out, k, kflip, out, s);
 }
 
 }  // extern "C"

@@ -63,6 +63,49 @@ __device__ __forceinline__ f32x4 mfma_f16_k32_half(const V8 &a, const V8 &b, f32
     return H == 0 ? __builtin_amdgcn_mfma_f32_16x16x16f16(a8.lo, b8.lo, c, 0, 0, 0)
                   : __builtin_amdgcn_mfma_f32_16x16x16f16(a8.hi, b8.hi, c, 0, 0, 0);
 }
+// ---- 16-bit STORAGE rows: which of the two 2-byte types a kernel's rows, scratch rows and one-plane weight fragments hold --------
+// bf16 storage (arith 3) and fp16 storage (arith 5, the reference's amp mode) share operand maps, fragment and LDS images and
+// the number of matrix instructions: a K = 32 product is two K = 16 instructions of the row type (the gfx942 forms: the
+// double-K f16 instruction is never issued, see above), and an fp32 result is rounded to the row type once, at its store --
+// fp16: beyond +-65504 it becomes +-inf as tensor.half() makes it, inf and NaN operands propagate through the products.
+enum Row16 : int { kRowsF32 = 0, kRowsBf16 = 1, kRowsF16 = 2 };
+template <class V8>
+__device__ __forceinline__ f32x4 mfma_f16_k32(const V8 &a, const V8 &b, f32x4 c) {
+    static_assert(sizeof(V8) == 16, "mfma_f16_k32: 8 fp16 per lane");
+    const u2_h16x8 a8 = __builtin_bit_cast(u2_h16x8, a), b8 = __builtin_bit_cast(u2_h16x8, b);
+    c = __builtin_amdgcn_mfma_f32_16x16x16f16(a8.lo, b8.lo, c, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_16x16x16f16(a8.hi, b8.hi, c, 0, 0, 0);
+}
+// the K = 32 product of one-plane 16-bit operands of row type H16 ? fp16 : bf16
+template <bool H16, class V8>
+__device__ __forceinline__ f32x4 mfma_rows16_k32(const V8 &a, const V8 &b, f32x4 c) {
+    if constexpr (H16) return mfma_f16_k32(a, b, c);
+    else return mfma_bf16_k32(a, b, c);
+}
+// two fp32 values -> one dword of two row-type values (element 0 in the low half), each rounded to nearest even
+template <bool H16>
+__device__ __forceinline__ uint32_t pack_rows16(float lo, float hi) {
+    if constexpr (H16) {
+        const u2_h16x2 h = {(_Float16)lo, (_Float16)hi};
+        return __builtin_bit_cast(uint32_t, h);
+    } else {
+        const __bf16 a = (__bf16)lo, b = (__bf16)hi;
+        return (uint32_t)__builtin_bit_cast(unsigned short, a) | ((uint32_t)__builtin_bit_cast(unsigned short, b) << 16);
+    }
+}
+// one dword of two row-type values -> fp32, exactly
+template <bool H16>
+__device__ __forceinline__ void unpack_rows16(uint32_t w, float &lo, float &hi) {
+    if constexpr (H16) {
+        const u2_h16x2 h = __builtin_bit_cast(u2_h16x2, w);
+        lo = (float)h[0];
+        hi = (float)h[1];
+    } else {      // a bf16 is the upper half of the fp32 with the same value
+        lo = __uint_as_float(w << 16);
+        hi = __uint_as_float(w & 0xffff0000u);
+    }
+}
+
 // the power of two s (and 1 / s) that puts m >= 0 into [2^14, 2^15); exponents clamped so that both stay normal floats
 __device__ __forceinline__ void f16x2_scale(float m, float &s, float &inv) {
     unsigned e = __float_as_uint(m) >> 23;
@@ -104,16 +147,17 @@ int launch_weight_fragments_batch(const int64_t *jobs, int n_jobs, int64_t total
 // Global pair schedule in bf16x3 arithmetic (conv_px3.hip); wf = arith-2 fragments.  -1 = shape not supported.
 bool conv_px3_supported(int cin, int cout);
 int launch_conv_px3(const char *who, const float *in, int cin, const float *wf, int cout, const int32_t *pair_idx,
-                    const int32_t *tile_k, const int32_t *n_tiles, int64_t capacity, float *y, hipStream_t st, bool b16 = false,
+                    const int32_t *tile_k, const int32_t *n_tiles, int64_t capacity, float *y, hipStream_t st,
+                    int rows16 = kRowsF32 /* Row16: rows, scratch rows and one-plane fragments (arith 3 / 5) of that type */,
                     int f16x2_k = 0 /* > 0: wf = the arith-4 (f16x2) fragments of a weight with this many offsets */);
 // the same kernel with the identity pair list: y[n_rows, cout] = in x B (+ bias), one offset (nn.Linear)
 int launch_linear_px3(const char *who, const float *in, int64_t n_rows, int cin, const float *wf, int cout,
-                      const float *bias, float *y, hipStream_t st, bool b16 = false, bool f16x2 = false);
+                      const float *bias, float *y, hipStream_t st, int rows16 = kRowsF32, bool f16x2 = false);
 
 // Weight gradient in bf16x3 arithmetic (conv_wgrad_x3.hip): 64 x 64-channel tiles, slabs as the f32 kernel.
 bool conv_wgrad_x3_supported(int ca, int cb, int k);
 int launch_conv_wgrad_x3(const float *a, int ca, const float *b, int cb, const int32_t *pairs, const int32_t *plan,
-                         int k, int swap, int g, int merge, float *slabs, hipStream_t st, bool b16);
+                         int k, int swap, int g, int merge, float *slabs, hipStream_t st, int rows16);
 int conv_wgrad_x3_merge(int ca, int cb);
 
 }  // namespace u2mkd

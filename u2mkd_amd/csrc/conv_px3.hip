@@ -32,6 +32,10 @@
 // image, no split, ONE v_mfma_f32_16x16x32_bf16 per 32 channels, fp32 accumulators -- with 64-channel steps where
 // cin allows (a row's step is again one full 128-byte line), weights = the one-plane fragments of
 // u2mkd_weight_fragments(arith 3), scratch rows y / outputs in bf16 (rounded once from the fp32 accumulator).
+//
+// FP16 STORAGE (B16 with H16; the reference's amp mode itself: autocast to half + GradScaler): the B16 pipeline, byte for byte
+// the same images and steps, on fp16 rows and the one-plane fp16 fragments of arith 5 -- two v_mfma_f32_16x16x16_f16 per 32
+// channels, scratch rows y / outputs rounded to fp16 once (beyond fp16's range: +-inf, not saturated).
 #include <stdlib.h>
 
 #include <type_traits>
@@ -75,7 +79,7 @@ __device__ __forceinline__ float px_dpp(float v) {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
 }
 
-template <int NW, int NBW, bool DENSE = false, bool B16 = false, int SC = 32, int TL = 1, bool F2 = false>
+template <int NW, int NBW, bool DENSE = false, bool B16 = false, int SC = 32, int TL = 1, bool F2 = false, bool H16 = false>
 __global__ void __launch_bounds__(64 * NW)
 conv_px3_kernel(const float *__restrict__ in, int cin, const float *__restrict__ wf, int cout,
                 const int32_t *__restrict__ pair_idx, const int32_t *__restrict__ tile_k,
@@ -83,6 +87,7 @@ conv_px3_kernel(const float *__restrict__ in, int cin, const float *__restrict__
                 int n_rows = 0, int k_total = 1) {
     static_assert(B16 ? (SC == 32 || SC == 64) : SC == 32, "step width");
     static_assert(!(F2 && B16), "f16x2 is an arithmetic of fp32 rows");
+    static_assert(!H16 || B16, "fp16 storage is a form of the 2-byte-row pipeline");
     constexpr int NT = 64 * NW, TN = 16 * NW * NBW;
     // bytes per row of the LDS image: 3 planes x 32 bf16 (or up to 64 bf16), NO pad; the 16-byte chunk c of a 64-byte plane
     // segment of tile row `row` sits at chunk c ^ 2 * bit 3 of row.  A ds_read_b128 is served in four 16-lane groups (rows
@@ -283,7 +288,7 @@ conv_px3_kernel(const float *__restrict__ in, int cin, const float *__restrict__
                     f32x4 c = acc[rb][n];
 #pragma unroll
                     for (int p = 0; p < NWF; ++p)
-                        c = mfma_bf16_k32(px_bf8(bw[u][NWF * n + p]), px_bf8(a[rb & 1][p]), c, 0, 0, 0);
+                        c = mfma_rows16_k32<H16>(px_bf8(bw[u][NWF * n + p]), px_bf8(a[rb & 1][p]), c);
                     acc[rb][n] = c;
                 }
                 continue;
@@ -340,7 +345,10 @@ conv_px3_kernel(const float *__restrict__ in, int cin, const float *__restrict__
                     if (cbw + n < ncb && (!DENSE || row < n_rows)) {
                         f32x4 o = acc[rb][n];
                         if (DENSE && bias) o += *reinterpret_cast<const f32x4 *>(bias + col);
-                        if (B16) {
+                        if (H16) {
+                            *reinterpret_cast<uint2 *>(reinterpret_cast<char *>(y) + ((size_t)row * cout + col) * 2) =
+                                make_uint2(pack_rows16<true>(o[0], o[1]), pack_rows16<true>(o[2], o[3]));
+                        } else if (B16) {
                             px_bf16x4 ob;
                             ob[0] = (__bf16)o[0]; ob[1] = (__bf16)o[1]; ob[2] = (__bf16)o[2]; ob[3] = (__bf16)o[3];
                             *reinterpret_cast<px_bf16x4 *>(reinterpret_cast<char *>(y) + ((size_t)row * cout + col) * 2) = ob;
@@ -392,13 +400,13 @@ static Px3Shape px3_shape(int cin, int cout) {
     return p;
 }
 
-template <bool DENSE, bool B16, int SC, bool F2 = false>
+template <bool DENSE, bool B16, int SC, bool F2 = false, bool H16 = false>
 static void px3_launch(const Px3Shape &p, dim3 grid, hipStream_t st, const float *in, int cin, const float *wf, int cout,
                        const int32_t *pair_idx, const int32_t *tile_k, const int32_t *n_tiles, float *y, const float *bias,
                        int n_rows, int k_total = 1) {
     const size_t lds = (size_t)2 * 64 * p.tl * 192;
 #define U2_PX3(NW_, NBW_, TL_)                                                                                                  \
-    hipLaunchKernelGGL((conv_px3_kernel<NW_, NBW_, DENSE, B16, SC, TL_, F2>), grid, dim3(64 * NW_), lds, st, in, cin, wf, cout, pair_idx, \
+    hipLaunchKernelGGL((conv_px3_kernel<NW_, NBW_, DENSE, B16, SC, TL_, F2, H16>), grid, dim3(64 * NW_), lds, st, in, cin, wf, cout, pair_idx, \
                        tile_k, n_tiles, y, bias, n_rows, k_total)
     if (p.tl == 2) {
         if (p.w3) U2_PX3(3, 2, 2); else U2_PX3(4, 2, 2);
@@ -410,9 +418,9 @@ static void px3_launch(const Px3Shape &p, dim3 grid, hipStream_t st, const float
 #undef U2_PX3
 }
 
-// b16: `in` and `y` are bf16 rows, wf = the arith-3 (one bf16 plane) fragments
+// rows16 (Row16): `in` and `y` are bf16 / fp16 rows, wf = the one-plane fragments of that type (arith 3 / 5)
 int launch_conv_px3(const char *who, const float *in, int cin, const float *wf, int cout, const int32_t *pair_idx,
-                    const int32_t *tile_k, const int32_t *n_tiles, int64_t capacity, float *y, hipStream_t st, bool b16,
+                    const int32_t *tile_k, const int32_t *n_tiles, int64_t capacity, float *y, hipStream_t st, int rows16,
                     int f16x2_k) {
     if (!conv_px3_supported(cin, cout)) return -1;
     const Px3Shape p = px3_shape(cin, cout);
@@ -424,15 +432,17 @@ int launch_conv_px3(const char *who, const float *in, int cin, const float *wf, 
     if (gx < 8) gx = 8;
     dim3 grid((unsigned)gx);
     if (f16x2_k > 0) px3_launch<false, false, 32, true>(p, grid, st, in, cin, wf, cout, pair_idx, tile_k, n_tiles, y, nullptr, 0, f16x2_k);
-    else if (!b16) px3_launch<false, false, 32>(p, grid, st, in, cin, wf, cout, pair_idx, tile_k, n_tiles, y, nullptr, 0);
+    else if (rows16 == kRowsF32) px3_launch<false, false, 32>(p, grid, st, in, cin, wf, cout, pair_idx, tile_k, n_tiles, y, nullptr, 0);
+    else if (rows16 == kRowsF16 && cin % 64 == 0) px3_launch<false, true, 64, false, true>(p, grid, st, in, cin, wf, cout, pair_idx, tile_k, n_tiles, y, nullptr, 0);
+    else if (rows16 == kRowsF16) px3_launch<false, true, 32, false, true>(p, grid, st, in, cin, wf, cout, pair_idx, tile_k, n_tiles, y, nullptr, 0);
     else if (cin % 64 == 0) px3_launch<false, true, 64>(p, grid, st, in, cin, wf, cout, pair_idx, tile_k, n_tiles, y, nullptr, 0);
     else px3_launch<false, true, 32>(p, grid, st, in, cin, wf, cout, pair_idx, tile_k, n_tiles, y, nullptr, 0);
     return check_launch(who);
 }
 
-// y[n_rows, cout] = in[n_rows, cin] x B (+ bias), B in the arith-2 (b16: arith-3) fragment order of ONE offset
+// y[n_rows, cout] = in[n_rows, cin] x B (+ bias), B in the arith-2 (rows16: arith-3 / arith-5) fragment order of ONE offset
 int launch_linear_px3(const char *who, const float *in, int64_t n_rows, int cin, const float *wf, int cout,
-                      const float *bias, float *y, hipStream_t st, bool b16, bool f16x2) {
+                      const float *bias, float *y, hipStream_t st, int rows16, bool f16x2) {
     if (!conv_px3_supported(cin, cout)) return -1;
     const Px3Shape p = px3_shape(cin, cout);
     const int gy = (int)ceil_div(cout, p.tn);
@@ -441,7 +451,9 @@ int launch_linear_px3(const char *who, const float *in, int64_t n_rows, int cin,
     if (gx < 8) gx = 8;
     dim3 grid((unsigned)gx);
     if (f16x2) px3_launch<true, false, 32, true>(p, grid, st, in, cin, wf, cout, nullptr, nullptr, nullptr, y, bias, (int)n_rows, 1);
-    else if (!b16) px3_launch<true, false, 32>(p, grid, st, in, cin, wf, cout, nullptr, nullptr, nullptr, y, bias, (int)n_rows);
+    else if (rows16 == kRowsF32) px3_launch<true, false, 32>(p, grid, st, in, cin, wf, cout, nullptr, nullptr, nullptr, y, bias, (int)n_rows);
+    else if (rows16 == kRowsF16 && cin % 64 == 0) px3_launch<true, true, 64, false, true>(p, grid, st, in, cin, wf, cout, nullptr, nullptr, nullptr, y, bias, (int)n_rows);
+    else if (rows16 == kRowsF16) px3_launch<true, true, 32, false, true>(p, grid, st, in, cin, wf, cout, nullptr, nullptr, nullptr, y, bias, (int)n_rows);
     else if (cin % 64 == 0) px3_launch<true, true, 64>(p, grid, st, in, cin, wf, cout, nullptr, nullptr, nullptr, y, bias, (int)n_rows);
     else px3_launch<true, true, 32>(p, grid, st, in, cin, wf, cout, nullptr, nullptr, nullptr, y, bias, (int)n_rows);
     return check_launch(who);

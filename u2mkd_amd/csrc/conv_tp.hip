@@ -98,7 +98,8 @@ __device__ __forceinline__ void split3(float x, __bf16 &h, __bf16 &m, __bf16 &l)
 // B_k[16 cb + r][32 s + 8 q .. +7], lane = r + 16 q: the operand fragment of v_mfma_f32_16x16x32_bf16
 // (lane l holds A[row l & 15][k = 8 (l >> 4) + j]).  One thread reads 8 reduction channels of one column
 // and writes the three 16-byte fragments.
-template <int PLANES>
+// H16 (PLANES == 1 only): the one plane holds fp16 values (arith 5, float -> _Float16) instead of bf16 ones (arith 3)
+template <int PLANES, bool H16 = false>
 __global__ void weight_fragments_x3_kernel(const float *__restrict__ w, int rows, int cols, int transpose,
                                            bf16x8 *__restrict__ wf, int64_t total) {
     int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -135,6 +136,12 @@ __global__ void weight_fragments_x3_kernel(const float *__restrict__ w, int rows
         f16x2_split2(x[6] * sc, x[7] * sc, vh4.w, vl4.w);
         o[0] = __builtin_bit_cast(bf16x8, vh4);
         o[64] = __builtin_bit_cast(bf16x8, vl4);
+        return;
+    }
+    if (H16) {              // fp16 storage: the weights rounded to fp16
+        static_assert(!H16 || PLANES == 1, "fp16 fragments are one plane");
+        o[0] = __builtin_bit_cast(bf16x8, make_uint4(pack_rows16<true>(x[0], x[1]), pack_rows16<true>(x[2], x[3]),
+                                                     pack_rows16<true>(x[4], x[5]), pack_rows16<true>(x[6], x[7])));
         return;
     }
     bf16x8 vh, vm, vl;
@@ -220,7 +227,8 @@ weight_absmax_finish_kernel(const int64_t *__restrict__ jobs) {
 // The same re-layout for MANY weights in one launch (u2mkd_weight_fragments_batch): a training step changes every
 // trainable weight at once (the optimizer step), and one latency-bound launch per weight -- ~5 us each, ~100 per step,
 // each in front of the first convolution that needs it -- becomes one launch behind the optimizer.  jobs[j] =
-// {w, wf, first unit, k, rows, cols, planes (3 = bf16x3, 1 = one bf16 plane), 0} as int64; a unit = one wave = 64 lanes
+// {w, wf, first unit, k, rows, cols, planes (3 = bf16x3, 2 = f16x2, 1 = one 16-bit plane), type of a one-plane job (0 = bf16,
+// arith 3; 1 = fp16, arith 5)} as int64; a unit = one wave = 64 lanes
 // x 8 reduction channels; job j owns units [first_j, first_j+1): 2 orientations x k rows cols / 512, transpose = 1 first
 // (the layout of u2mkd_weight_fragments with transpose = 2).
 __global__ void __launch_bounds__(64)
@@ -270,6 +278,11 @@ weight_fragments_batch_kernel(const int64_t *__restrict__ jobs, int n_jobs) {
         o[64] = __builtin_bit_cast(bf16x8, vl4);
         return;
     }
+    if (planes == 1 && jb[7] == 1) {      // fp16 storage (arith 5)
+        o[0] = __builtin_bit_cast(bf16x8, make_uint4(pack_rows16<true>(x[0], x[1]), pack_rows16<true>(x[2], x[3]),
+                                                     pack_rows16<true>(x[4], x[5]), pack_rows16<true>(x[6], x[7])));
+        return;
+    }
     bf16x8 vh, vm, vl;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -306,11 +319,13 @@ conv_tp_kernel(const float *__restrict__ in, const float *__restrict__ wf, int c
     int n_blocks = 0;
     if (STAMP) { t_rt0 = __builtin_amdgcn_s_memrealtime(); t_c0 = __builtin_amdgcn_s_memtime(); }
     // AR: 1 = fp32 rows, f32 MFMA; 2 = fp32 rows, bf16x3; 3 = BF16 STORAGE: `in` and `out` are bf16 rows, wf = one bf16
-    // plane (u2mkd_weight_fragments arith 3), one v_mfma_f32_16x16x32_bf16 per 32-channel step, fp32 accumulation in the
+    // plane (u2mkd_weight_fragments arith 3), two v_mfma_f32_16x16x16_bf16 per 32-channel step, fp32 accumulation in the
     // LDS tile, outputs rounded to bf16 once (BASELINE.json configs[4]: half the gather bytes, no run-time split)
     // 4 = fp32 rows, f16x2: two fp16 planes of every gathered row scaled by a per-row power of two, three products per 16 channels
     // (conv_internal.h), the row's and the weight tensor's scales taken out again when the block's products join the output tile
-    constexpr bool X3 = AR == 2, B16 = AR == 3, F2 = AR == 4;
+    // 5 = FP16 STORAGE: the structure of 3 on fp16 rows and one fp16 weight plane (arith 5), two v_mfma_f32_16x16x16_f16 per
+    // 32-channel step, outputs rounded to fp16 once (beyond fp16's range: +-inf)
+    constexpr bool X3 = AR == 2, H16 = AR == 5, B16 = AR == 3 || H16, F2 = AR == 4;      // (B16: 2-byte rows of either type)
     constexpr int T = 64, NT = 64 * NW, TN = 16 * NW * NBW, NJ = CIN / 16;
     constexpr int OS = TN + 4;                    // output tile row stride (floats)
     // gathered-row image: fp32 rows, or (X3) three bf16 planes h | m | l of CIN elements per row; + 16 B pad
@@ -667,8 +682,8 @@ conv_tp_kernel(const float *__restrict__ in, const float *__restrict__ wf, int c
                 } else if (B16) {
 #pragma unroll
                     for (int sk = 0; sk < CIN / 32; ++sk) {
-                        if (sk & 1) acc1 = mfma_bf16_k32(as_bf8(bw[SB ? 0 : (u & 1)][sk][n]), as_bf8(a[sk]), acc1, 0, 0, 0);
-                        else acc0 = mfma_bf16_k32(as_bf8(bw[SB ? 0 : (u & 1)][sk][n]), as_bf8(a[sk]), acc0, 0, 0, 0);
+                        if (sk & 1) acc1 = mfma_rows16_k32<H16>(as_bf8(bw[SB ? 0 : (u & 1)][sk][n]), as_bf8(a[sk]), acc1);
+                        else acc0 = mfma_rows16_k32<H16>(as_bf8(bw[SB ? 0 : (u & 1)][sk][n]), as_bf8(a[sk]), acc0);
                     }
                 } else {
                     // two interleaved accumulation chains (16x16x4 f32: 40-cycle dependent latency, 32 issue)
@@ -747,7 +762,10 @@ conv_tp_kernel(const float *__restrict__ in, const float *__restrict__ wf, int c
                 }
                 if (rr_.ep_relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
             }
-            if (B16) {
+            if (H16) {
+                *reinterpret_cast<uint2 *>(reinterpret_cast<char *>(out) + ((size_t)rid * cout + col) * 2) =
+                    make_uint2(pack_rows16<true>(v.x, v.y), pack_rows16<true>(v.z, v.w));
+            } else if (B16) {
                 bf16x4 b;
                 b[0] = (__bf16)v.x; b[1] = (__bf16)v.y; b[2] = (__bf16)v.z; b[3] = (__bf16)v.w;
                 *reinterpret_cast<bf16x4 *>(reinterpret_cast<char *>(out) + ((size_t)rid * cout + col) * 2) = b;
@@ -786,7 +804,7 @@ static void launch_tp(dim3 grid, int K, hipStream_t st, const float *in, const f
                       const int32_t *order, RowRange rr, const int32_t *items, const int32_t *n_items, int kflip,
                       float *out, unsigned long long *stamps = nullptr) {
     constexpr int TN = 16 * NW * NBW;
-    const size_t lds = (size_t)64 * (TN + 4) * 4 + (size_t)2 * 16 * ((AR == 2 ? 6 * CIN : AR == 3 ? 2 * CIN : 4 * CIN) + 4 * kTpPad) + (size_t)(K + 1) * 64 * 4 + 32 * 4 + 64 * 4 +
+    const size_t lds = (size_t)64 * (TN + 4) * 4 + (size_t)2 * 16 * ((AR == 2 ? 6 * CIN : (AR == 3 || AR == 5) ? 2 * CIN : 4 * CIN) + 4 * kTpPad) + (size_t)(K + 1) * 64 * 4 + 32 * 4 + 64 * 4 +
                        (size_t)(4 * K + 8) * 4 + (AR == 4 ? 2 * 16 * 4 : 0) + U2MKD_TP_EXTRA_LDS;
     const int n_tiles = (int)ceil_div(rr.end - rr.begin, 64);
     // one resident wave of workgroups at most (they deal the items among themselves, lightest first)
@@ -828,7 +846,7 @@ bool conv_tp_f16x2_supported(int cin) { return cin == 32 || cin == 64 || cin == 
 // arithmetic of the tile-pair kernel: 1 = f32 MFMA (bitwise fma chain), 2 = bf16x3 (fp32 accuracy, 2.7x fewer
 // matrix-pipe cycles); 0 = the library default (U2MKD_CONV_ARITH=f32|bf16x3, default bf16x3)
 int conv_tp_arith(int arith) {
-    if (arith >= 1 && arith <= 4) return arith;
+    if (arith >= 1 && arith <= 5) return arith;
     static const int dflt = [] {
         const char *e = getenv("U2MKD_CONV_ARITH");
         return (e && e[0] == 'f' && e[1] == '3') ? 1 : 2;      // ("f16x2" concerns the tile kernel only: u2mkd_conv_tiles_arith)
@@ -850,6 +868,7 @@ int launch_conv_tp(const char *who, const float *in, int cin, const float *wf, i
 #define U2_TP(NW_, NBW_, CIN_)                                                                                          \
     do {                                                                                                                \
         if (ar == 3) launch_tp<NW_, NBW_, CIN_, false, 3>(grid, k, st, in, wf, cout, nbr, order, rr, items, n_items, kflip, out);  \
+        else if (ar == 5) launch_tp<NW_, NBW_, CIN_, false, 5>(grid, k, st, in, wf, cout, nbr, order, rr, items, n_items, kflip, out);  \
         else if (ar == 4 && CIN_ != 96) launch_tp<NW_, NBW_, (CIN_ != 96 ? CIN_ : 64), false, 4>(grid, k, st, in, wf, cout, nbr, order, rr, items, n_items, kflip, out);  \
         else if (x3) launch_tp<NW_, NBW_, CIN_, false, 2>(grid, k, st, in, wf, cout, nbr, order, rr, items, n_items, kflip, out);  \
         else launch_tp<NW_, NBW_, CIN_, false, 1>(grid, k, st, in, wf, cout, nbr, order, rr, items, n_items, kflip, out);    \
@@ -873,14 +892,14 @@ int launch_conv_tp(const char *who, const float *in, int cin, const float *wf, i
 
 size_t weight_fragments_bytes(int k, int rows, int cols, int arith) {
     const int ar = conv_tp_arith(arith);
-    return (size_t)k * rows * cols * (ar == 2 ? 6 : ar == 3 ? 2 : 4) + (ar == 4 ? 16 : 0);      // (f16x2: two fp16 planes + the scale trailer)
+    return (size_t)k * rows * cols * (ar == 2 ? 6 : (ar == 3 || ar == 5) ? 2 : 4) + (ar == 4 ? 16 : 0);      // (f16x2: two fp16 planes + the scale trailer)
 }
 
 int launch_weight_fragments(const float *w, int k, int rows, int cols, int transpose, int arith, float *wf, hipStream_t st) {
     const int64_t elems = (int64_t)k * rows * cols;
     if (elems == 0) return 0;
     const int ar = conv_tp_arith(arith);
-    if (ar == 2 || ar == 3 || ar == 4) {
+    if (ar >= 2 && ar <= 5) {
         const int64_t total = elems / 8;          // one thread per (offset, column, 8 reduction channels)
         // one-wave workgroups: the kernel is a single round of loads and stores per thread (latency-bound), and 27 x 64 x 64
         // weights are only 432 waves -- as 256-thread workgroups they sat on 108 of the 256 CUs
@@ -895,6 +914,9 @@ int launch_weight_fragments(const float *w, int k, int rows, int cols, int trans
                                reinterpret_cast<bf16x8 *>(wf), total);
         } else if (ar == 2)
             hipLaunchKernelGGL(weight_fragments_x3_kernel<3>, grid, dim3(bt), 0, st, w, rows, cols, transpose,
+                               reinterpret_cast<bf16x8 *>(wf), total);
+        else if (ar == 5)
+            hipLaunchKernelGGL((weight_fragments_x3_kernel<1, true>), grid, dim3(bt), 0, st, w, rows, cols, transpose,
                                reinterpret_cast<bf16x8 *>(wf), total);
         else
             hipLaunchKernelGGL(weight_fragments_x3_kernel<1>, grid, dim3(bt), 0, st, w, rows, cols, transpose,

@@ -77,8 +77,9 @@ __device__ __forceinline__ wx_bf16x8 wx_frag(const char *base_lo, const char *ba
     return __builtin_bit_cast(wx_bf16x8, v);
 }
 
-// B16: a and b are BF16 rows (bf16 storage): no split, ONE plane in the image, one MFMA per product.
-template <bool B16>
+// B16: a and b are 2-byte rows (bf16 storage; H16: fp16 storage): no split, ONE plane in the image, one K = 32 product of the
+// row type (conv_internal.h: mfma_rows16_k32) per tile and chunk; the slabs are fp32 either way.
+template <bool B16, bool H16 = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4)))
 conv_wgrad_x3_kernel(const float *__restrict__ a, int ca, const float *__restrict__ b, int cb,
                      const int32_t *__restrict__ pairs, const int32_t *__restrict__ plan, int K, int swap,
@@ -190,7 +191,7 @@ conv_wgrad_x3_kernel(const float *__restrict__ a, int ca, const float *__restric
             for (int n = 0; n < 2; ++n) {
                 f32x4 c = acc[m][n];
                 if (B16) {
-                    c = mfma_bf16_k32(fa[m][0], fb[n][0], c, 0, 0, 0);
+                    c = mfma_rows16_k32<H16>(fa[m][0], fb[n][0], c);
                 } else {
                     // the six partial products, low order first (plane 0 = h, 1 = m, 2 = l)
                     c = mfma_bf16_k32(fa[m][NPL - 1], fb[n][0], c, 0, 0, 0);
@@ -266,10 +267,13 @@ conv_wgrad_x3_kernel(const float *__restrict__ a, int ca, const float *__restric
 bool conv_wgrad_x3_supported(int ca, int cb, int k) { return ca % 4 == 0 && cb % 4 == 0 && ca >= 4 && cb >= 4 && k <= 63; }
 
 int launch_conv_wgrad_x3(const float *a, int ca, const float *b, int cb, const int32_t *pairs, const int32_t *plan,
-                         int k, int swap, int g, int merge, float *slabs, hipStream_t st, bool b16) {
+                         int k, int swap, int g, int merge, float *slabs, hipStream_t st, int rows16) {
     const int tiles_a = (ca + 63) / 64, tiles_b = (cb + 63) / 64;
     dim3 grid((g + merge - 1) / merge, tiles_a * tiles_b);
-    if (b16)
+    if (rows16 == kRowsF16)
+        hipLaunchKernelGGL((conv_wgrad_x3_kernel<true, true>), grid, dim3(256), (size_t)2 * kWxCP * kWxRow, st, a, ca, b, cb, pairs,
+                           plan, k, swap, merge, slabs);
+    else if (rows16 == kRowsBf16)
         hipLaunchKernelGGL(conv_wgrad_x3_kernel<true>, grid, dim3(256), (size_t)2 * kWxCP * kWxRow, st, a, ca, b, cb, pairs,
                            plan, k, swap, merge, slabs);
     else

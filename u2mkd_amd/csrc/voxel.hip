@@ -192,8 +192,8 @@ __global__ void segment_sum_kernel(const float *__restrict__ src, int c4, const 
     reinterpret_cast<float4 *>(out)[t] = acc;
 }
 
-// ---- the row movers on float OR bf16 rows (common.h ld4 / st4), 4 channels per thread; the fp32 entries keep the
-// kernels above (bit-for-bit the round-2 arithmetic), the bf16-storage entries use these with T = bf16row: sums in fp32
+// ---- the row movers on float, bf16 OR fp16 rows (common.h ld4 / st4), 4 channels per thread; the fp32 entries keep the
+// kernels above (bit-for-bit the round-2 arithmetic), the 16-bit-storage entries use these with T = bf16row / _Float16: sums in fp32
 // in the same fixed order, one rounding at the store
 template <typename T>
 __global__ void voxelize_bwd_rows_kernel(const T *__restrict__ gout, const int32_t *__restrict__ idx,
@@ -507,40 +507,76 @@ int u2mkd_segment_sum(const float *src, int32_t c, const int32_t *entry_row, con
     return check_launch("u2mkd_segment_sum");
 }
 
-/* ---- bf16 rows (feature rows in and out are bf16 [., c], c a multiple of 4; indices, weights, counts as above) ---- */
+}  // extern "C"
+
+/* ---- 16-bit rows (feature rows in and out are bf16 or fp16 [., c], c a multiple of 4; indices, weights, counts as above): one
+ * implementation per entry pair, T = the row type, `who` = the entry's name ---- */
+template <typename T>
+static int voxelize_backward_rows(const char *who, const void *grad_out, const int32_t *idx, const int32_t *counts, int64_t n,
+                                  int64_t nv, int32_t c, void *grad_feats, u2mkd_stream_t s) {
+    if (n == 0 || c == 0) return 0;
+    U2_REQUIRE(grad_out && idx && counts && grad_feats, "%s: null pointer", who);
+    U2_REQUIRE(c % 4 == 0, "%s: c=%d must be a multiple of 4", who, c);
+    int64_t total = n * (c / 4);
+    hipLaunchKernelGGL(voxelize_bwd_rows_kernel<T>, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, as_stream(s),
+                       reinterpret_cast<const T *>(grad_out), idx, counts, n, nv, c / 4, reinterpret_cast<T *>(grad_feats));
+    return check_launch(who);
+}
+
+template <typename T>
+static int devoxelize_forward_rows(const char *who, const void *feats, const int32_t *idx, const float *w, int64_t n, int32_t c,
+                                   void *out, u2mkd_stream_t s) {
+    if (n == 0 || c == 0) return 0;
+    U2_REQUIRE(feats && idx && w && out, "%s: null pointer", who);
+    U2_REQUIRE(c % 4 == 0, "%s: c=%d must be a multiple of 4", who, c);
+    int64_t total = n * (c / 4);
+    hipLaunchKernelGGL(devoxelize_fwd_rows_kernel<T>, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, as_stream(s),
+                       reinterpret_cast<const T *>(feats), idx, w, n, c / 4, reinterpret_cast<T *>(out));
+    return check_launch(who);
+}
+
+template <typename T>
+static int segment_sum_rows(const char *who, const void *src, int32_t c, const int32_t *entry_row, const float *entry_w,
+                            const int32_t *seg_offsets, int64_t nv, int32_t mean, void *out, u2mkd_stream_t s) {
+    if (nv == 0 || c == 0) return 0;
+    U2_REQUIRE(src && entry_row && seg_offsets && out, "%s: null pointer", who);
+    U2_REQUIRE(c % 4 == 0, "%s: c=%d must be a multiple of 4", who, c);
+    int64_t total = nv * (c / 4);
+    hipLaunchKernelGGL(segment_sum_rows_kernel<T>, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, as_stream(s),
+                       reinterpret_cast<const T *>(src), c / 4, entry_row, entry_w, seg_offsets, nv, mean, reinterpret_cast<T *>(out));
+    return check_launch(who);
+}
+
+extern "C" {
+
 int u2mkd_voxelize_backward_bf16(const void *grad_out, const int32_t *idx, const int32_t *counts, int64_t n, int64_t nv,
                                  int32_t c, void *grad_feats, u2mkd_stream_t s) {
-    if (n == 0 || c == 0) return 0;
-    U2_REQUIRE(grad_out && idx && counts && grad_feats, "u2mkd_voxelize_backward_bf16: null pointer");
-    U2_REQUIRE(c % 4 == 0, "u2mkd_voxelize_backward_bf16: c=%d must be a multiple of 4", c);
-    int64_t total = n * (c / 4);
-    hipLaunchKernelGGL(voxelize_bwd_rows_kernel<bf16row>, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, as_stream(s),
-                       reinterpret_cast<const bf16row *>(grad_out), idx, counts, n, nv, c / 4,
-                       reinterpret_cast<bf16row *>(grad_feats));
-    return check_launch("u2mkd_voxelize_backward_bf16");
+    return voxelize_backward_rows<bf16row>("u2mkd_voxelize_backward_bf16", grad_out, idx, counts, n, nv, c, grad_feats, s);
+}
+
+int u2mkd_voxelize_backward_f16(const void *grad_out, const int32_t *idx, const int32_t *counts, int64_t n, int64_t nv,
+                                int32_t c, void *grad_feats, u2mkd_stream_t s) {
+    return voxelize_backward_rows<_Float16>("u2mkd_voxelize_backward_f16", grad_out, idx, counts, n, nv, c, grad_feats, s);
 }
 
 int u2mkd_devoxelize_forward_bf16(const void *feats, const int32_t *idx, const float *w, int64_t n, int32_t c, void *out,
                                   u2mkd_stream_t s) {
-    if (n == 0 || c == 0) return 0;
-    U2_REQUIRE(feats && idx && w && out, "u2mkd_devoxelize_forward_bf16: null pointer");
-    U2_REQUIRE(c % 4 == 0, "u2mkd_devoxelize_forward_bf16: c=%d must be a multiple of 4", c);
-    int64_t total = n * (c / 4);
-    hipLaunchKernelGGL(devoxelize_fwd_rows_kernel<bf16row>, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, as_stream(s),
-                       reinterpret_cast<const bf16row *>(feats), idx, w, n, c / 4, reinterpret_cast<bf16row *>(out));
-    return check_launch("u2mkd_devoxelize_forward_bf16");
+    return devoxelize_forward_rows<bf16row>("u2mkd_devoxelize_forward_bf16", feats, idx, w, n, c, out, s);
+}
+
+int u2mkd_devoxelize_forward_f16(const void *feats, const int32_t *idx, const float *w, int64_t n, int32_t c, void *out,
+                                 u2mkd_stream_t s) {
+    return devoxelize_forward_rows<_Float16>("u2mkd_devoxelize_forward_f16", feats, idx, w, n, c, out, s);
 }
 
 int u2mkd_segment_sum_bf16(const void *src, int32_t c, const int32_t *entry_row, const float *entry_w,
                            const int32_t *seg_offsets, int64_t nv, int32_t mean, void *out, u2mkd_stream_t s) {
-    if (nv == 0 || c == 0) return 0;
-    U2_REQUIRE(src && entry_row && seg_offsets && out, "u2mkd_segment_sum_bf16: null pointer");
-    U2_REQUIRE(c % 4 == 0, "u2mkd_segment_sum_bf16: c=%d must be a multiple of 4", c);
-    int64_t total = nv * (c / 4);
-    hipLaunchKernelGGL(segment_sum_rows_kernel<bf16row>, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, as_stream(s),
-                       reinterpret_cast<const bf16row *>(src), c / 4, entry_row, entry_w, seg_offsets, nv, mean,
-                       reinterpret_cast<bf16row *>(out));
-    return check_launch("u2mkd_segment_sum_bf16");
+    return segment_sum_rows<bf16row>("u2mkd_segment_sum_bf16", src, c, entry_row, entry_w, seg_offsets, nv, mean, out, s);
+}
+
+int u2mkd_segment_sum_f16(const void *src, int32_t c, const int32_t *entry_row, const float *entry_w,
+                          const int32_t *seg_offsets, int64_t nv, int32_t mean, void *out, u2mkd_stream_t s) {
+    return segment_sum_rows<_Float16>("u2mkd_segment_sum_f16", src, c, entry_row, entry_w, seg_offsets, nv, mean, out, s);
 }
 
 int u2mkd_ti_weights(const float *coords, const int64_t *idx_kn, int64_t n, float scale, float *w_n8,

@@ -288,14 +288,14 @@ class _SegmentMap(torch.autograd.Function):
         from .torchsparse.nn import functional as spf
         ctx.bwd, ctx.n_src, ctx.in_dtype = bwd, src.shape[0], src.dtype
         erow, ew, seg = fwd
-        # bf16 rows stay bf16 (bf16 storage under autocast); anything else is moved as fp32
-        return spf._segment_sum(spf._rows(src, src.dtype == torch.bfloat16), erow, ew, seg, n_dst, False)
+        # bf16 / fp16 rows stay as they are (16-bit storage under autocast); anything else is moved as fp32
+        return spf._segment_sum(spf._rows(src, spf._moved16(src.dtype)), erow, ew, seg, n_dst, False)
 
     @staticmethod
     def backward(ctx, g):
         from .torchsparse.nn import functional as spf
         erow, ew, seg = ctx.bwd
-        gs = spf._segment_sum(spf._rows(g, g.dtype == torch.bfloat16), erow, ew, seg, ctx.n_src, False)
+        gs = spf._segment_sum(spf._rows(g, spf._moved16(g.dtype)), erow, ew, seg, ctx.n_src, False)
         return (gs if gs.dtype == ctx.in_dtype else gs.to(ctx.in_dtype)), None, None, None
 
 
@@ -434,7 +434,7 @@ def l2c_scatter(point_feats, pixel_coordinates, masks, ifh, ifw, n_scales):
     from .torchsparse.nn import functional as spf
     B, ncam, C = len(masks), masks[0].shape[0], point_feats.shape[1]
     sizes = list(_l2c_grids(ifh, ifw, n_scales))
-    if (_L2C_COMBINE and point_feats.dtype == torch.float32 and not spf.bf16_rows() and 1 <= n_scales <= 4 and B * ncam <= 65535
+    if (_L2C_COMBINE and point_feats.dtype == torch.float32 and spf.row_dtype() is None and 1 <= n_scales <= 4 and B * ncam <= 65535
             and sizes[0] == (ifh, ifw)):
         grids = [_SegmentMap.apply(point_feats, *l2c_plan(pixel_coordinates, masks, ch, cw)) for ch, cw in sizes]
         if all(g.dtype == torch.float32 for g in grids):

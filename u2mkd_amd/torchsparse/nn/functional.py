@@ -128,13 +128,58 @@ def bf16_rows() -> bool:
     torchsparse v1.4.0 decorates its conv / voxelize / devoxelize functions ``custom_fwd(cast_inputs=torch.half)``
     (SURVEY.md Appendix A-6), so under the reference's amp (core/nusc_trainers.py:285) rows travel in half between
     them and nn.BatchNorm1d passes half through; here the reduced type is bf16 (BASELINE.json configs[4]), every
-    accumulation, statistic and weight gradient stays fp32.  fp16 autocast keeps fp32 rows (no fp16 kernels)."""
+    accumulation, statistic and weight gradient stays fp32.  (fp16 autocast: ``row_dtype``.)"""
     return _BF16_ROWS and torch.is_autocast_enabled('cuda') and torch.get_autocast_dtype('cuda') == torch.bfloat16
 
 
-def _rows(t, b16):
-    """contiguous rows in the storage type of the call"""
-    return t.contiguous().to(torch.bfloat16 if b16 else torch.float32)
+# ------------------------------------------------------------ fp16 storage
+_F16_ROWS = os.environ.get('U2MKD_F16_ROWS', '1') != '0'        # 0: fp16 autocast keeps fp32 rows between the sparse operators
+_ROW_SWITCH = {torch.bfloat16: _BF16_ROWS, torch.float16: _F16_ROWS}
+
+
+def row_dtype():
+    """The reduced dtype the sparse operators keep their feature rows in under the current autocast state: ``None`` (no
+    autocast, or its row switch is off: fp32 rows), ``torch.bfloat16`` (``bf16_rows()``) or ``torch.float16`` -- the
+    reference's own amp mode (autocast to half + GradScaler, core/nusc_trainers.py:285), where torchsparse keeps conv,
+    voxelize and devoxelize rows in half.  Accumulations, statistics, master weights and weight gradients are fp32 in both;
+    an fp16 row value beyond +-65504 is stored as inf (never saturated), which is what GradScaler looks for."""
+    if not torch.is_autocast_enabled('cuda'):
+        return None
+    return _stored16(torch.get_autocast_dtype('cuda'))
+
+
+def _stored16(dtype):
+    """``dtype`` if rows that arrive in it stay in it (a 16-bit row type whose switch is on), else None (fp32 rows)"""
+    return dtype if _ROW_SWITCH.get(dtype, False) else None
+
+
+def _moved16(dtype):
+    """``dtype`` if the row movers (voxelize / devoxelize backward, fusion's segment sums) carry rows that arrive in it as they
+    are: bf16 always (U2MKD_BF16_ROWS never changed that), fp16 unless U2MKD_F16_ROWS=0; else None (moved as fp32)"""
+    return dtype if (dtype == torch.bfloat16 or (dtype == torch.float16 and _F16_ROWS)) else None
+
+
+def _rows(t, rt):
+    """contiguous rows in the storage type of the call: ``rt`` = a 16-bit row dtype, or None = fp32"""
+    return t.contiguous().to(rt or torch.float32)
+
+
+_ENTRY_SUFFIX = {torch.bfloat16: '_bf16', torch.float16: '_f16'}
+
+
+def _entry(base, dtype):
+    """The C entry ``base`` for rows of ``dtype``: u2mkd_x / u2mkd_x_bf16 / u2mkd_x_f16 (include/u2mkd_hip.h)"""
+    return base + _ENTRY_SUFFIX.get(dtype, '')
+
+
+def _row_code(dtype):
+    """the row-dtype argument of the BatchNorm entries: 0 = fp32, 1 = bf16, 2 = fp16"""
+    return 1 if dtype == torch.bfloat16 else (2 if dtype == torch.float16 else 0)
+
+
+def _arith16(dtype):
+    """u2mkd_weight_fragments' arith of the ONE weight plane that goes with 16-bit rows: 3 = bf16, 5 = fp16"""
+    return 5 if dtype == torch.float16 else 3
 
 
 # U2MKD_PREFETCH_PLANS=0 (default): every derived index structure (tile / pair schedules, weight-gradient pairs, the scatter plans
@@ -181,10 +226,10 @@ def _plan(t: torch.Tensor, name: str, build, *deps):
 
 
 def _segment_sum(src, erow, ew, seg, nv, mean):
-    """rows of src (fp32 or bf16: the output has the same type) summed per destination segment"""
+    """rows of src (fp32, bf16 or fp16: the output has the same type) summed per destination segment"""
     c = src.shape[1]
     out = torch.empty(nv, c, dtype=src.dtype, device=src.device)
-    L.call('u2mkd_segment_sum_bf16' if src.dtype == torch.bfloat16 else 'u2mkd_segment_sum', L.ptr(src), c, L.ptr(erow),
+    L.call(_entry('u2mkd_segment_sum', src.dtype), L.ptr(src), c, L.ptr(erow),
            L.ptr(ew), L.ptr(seg), nv, int(mean), L.ptr(out), L.stream())
     return out
 
@@ -194,8 +239,8 @@ class VoxelizeFunction(Function):
     @staticmethod
     def forward(ctx, feats, coords, counts):
         L.require_cuda(feats, coords, counts)
-        b16 = bf16_rows() and feats.shape[1] % 4 == 0 and feats.shape[1] >= 16    # (coordinate means stay fp32: c = 4)
-        feats = _rows(feats, b16)
+        rt = row_dtype() if (feats.shape[1] % 4 == 0 and feats.shape[1] >= 16) else None    # (coordinate means stay fp32: c = 4)
+        feats = _rows(feats, rt)
         coords = _i32(coords).contiguous()
         counts = _i32(counts).contiguous()
         n, c = feats.shape
@@ -217,11 +262,10 @@ class VoxelizeFunction(Function):
     @staticmethod
     def backward(ctx, grad_output):
         coords, counts, n = ctx.for_backwards
-        b16 = grad_output.dtype == torch.bfloat16 and grad_output.shape[1] % 4 == 0
-        g = _rows(grad_output, b16)
+        g = _rows(grad_output, _moved16(grad_output.dtype) if grad_output.shape[1] % 4 == 0 else None)
         nv, c = g.shape
         gi = torch.empty(n, c, dtype=g.dtype, device=g.device)
-        L.call('u2mkd_voxelize_backward_bf16' if b16 else 'u2mkd_voxelize_backward', L.ptr(g), L.ptr(coords),
+        L.call(_entry('u2mkd_voxelize_backward', g.dtype), L.ptr(g), L.ptr(coords),
                L.ptr(counts), n, nv, c, L.ptr(gi), L.stream())
         return gi, None, None
 
@@ -250,15 +294,14 @@ class DevoxelizeFunction(Function):
     @staticmethod
     def forward(ctx, feats, coords, weights):
         L.require_cuda(feats, coords, weights)
-        b16 = bf16_rows() and feats.shape[1] % 4 == 0 and feats.shape[1] >= 16
-        feats = _rows(feats, b16)
+        feats = _rows(feats, row_dtype() if (feats.shape[1] % 4 == 0 and feats.shape[1] >= 16) else None)
         coords = _i32(coords).contiguous()
         weights = weights.contiguous().float()
         nv, c = feats.shape
         n = coords.shape[0]
         assert coords.shape == (n, 8) and weights.shape == (n, 8), (coords.shape, weights.shape)
         out = torch.empty(n, c, dtype=feats.dtype, device=feats.device)
-        L.call('u2mkd_devoxelize_forward_bf16' if b16 else 'u2mkd_devoxelize_forward', L.ptr(feats), L.ptr(coords),
+        L.call(_entry('u2mkd_devoxelize_forward', feats.dtype), L.ptr(feats), L.ptr(coords),
                L.ptr(weights), n, c, L.ptr(out), L.stream())
         ctx.for_backwards = (coords, weights, nv)
         return out
@@ -266,7 +309,7 @@ class DevoxelizeFunction(Function):
     @staticmethod
     def backward(ctx, grad_output):
         coords, weights, nv = ctx.for_backwards
-        g = _rows(grad_output, grad_output.dtype == torch.bfloat16 and grad_output.shape[1] % 4 == 0)
+        g = _rows(grad_output, _moved16(grad_output.dtype) if grad_output.shape[1] % 4 == 0 else None)
         n, c = g.shape
         if n == 0:
             return torch.zeros(nv, c, dtype=g.dtype, device=g.device), None, None
@@ -690,9 +733,9 @@ class TileSchedule:
                    L.ptr(self.order), L.ptr(self.items), L.ptr(self.n_items), self.n, self.k, int(kflip), ar, L.ptr(sc), L.ptr(sh),
                    L.ptr(res), int(relu), L.ptr(out), L.stream())
             return out
-        if feats.dtype == torch.bfloat16:        # bf16 storage: rows in and out bf16, one bf16 weight plane
-            wf = _weight_layout(weight, transpose, True, arith=3)
-            L.call('u2mkd_conv_forward_tiles_bf16', L.ptr(feats), n_in, cin, L.ptr(wf), cout, L.ptr(self.nbr_s),
+        if feats.dtype != torch.float32:         # bf16 / fp16 storage: rows in and out in that type, one weight plane of it
+            wf = _weight_layout(weight, transpose, True, arith=_arith16(feats.dtype))
+            L.call(_entry('u2mkd_conv_forward_tiles', feats.dtype), L.ptr(feats), n_in, cin, L.ptr(wf), cout, L.ptr(self.nbr_s),
                    L.ptr(self.order), L.ptr(self.items), L.ptr(self.n_items), self.n, self.k, int(kflip), L.ptr(out),
                    L.stream())
         elif L.load().u2mkd_conv_tiles_supported(cin, cout, self.k):
@@ -788,10 +831,10 @@ class PairSchedule:
         if n_rows == 0:
             return out
         y = _scratch(self.cap * cout * 4, feats.device)
-        if feats.dtype == torch.bfloat16:        # bf16 storage (wt = the arith-3 fragments): scratch rows y in bf16 too
-            L.call('u2mkd_conv_forward_pairs_bf16', L.ptr(feats), n, cin, L.ptr(wt), cout, L.ptr(idx), L.ptr(self.tile_k),
+        if feats.dtype != torch.float32:         # bf16 / fp16 storage (wt = the arith-3 / arith-5 fragments): scratch rows y in that type too
+            L.call(_entry('u2mkd_conv_forward_pairs', feats.dtype), L.ptr(feats), n, cin, L.ptr(wt), cout, L.ptr(idx), L.ptr(self.tile_k),
                    L.ptr(self.meta), self.cap, self.k, L.ptr(y), st)
-            L.call('u2mkd_pairs_gather_sum_bf16', L.ptr(y), L.ptr(pos), n_rows, self.k, cout, L.ptr(out), st)
+            L.call(_entry('u2mkd_pairs_gather_sum', feats.dtype), L.ptr(y), L.ptr(pos), n_rows, self.k, cout, L.ptr(out), st)
             return out
         if fragments:
             L.call('u2mkd_conv_forward_pairs_f16x2' if fragments == 2 else 'u2mkd_conv_forward_pairs_x3', L.ptr(feats), n, cin, L.ptr(wt), cout, L.ptr(idx), L.ptr(self.tile_k),
@@ -1003,11 +1046,12 @@ def _conv_os(feats, weight, transpose, cout, kmap, inverse, n_rows, kflip, epilo
     gradient of a symmetric (submanifold) map computed on the forward table with mirrored offsets -- in the
     pair schedule that is simply the swapped-role walk."""
     out = torch.empty(n_rows, cout, dtype=feats.dtype, device=feats.device)
-    if feats.dtype == torch.bfloat16 and not L.load().u2mkd_conv_tiles_supported(feats.shape[1], cout, kmap.k):
-        # bf16 storage, every shape the tile kernel has no instantiation for (_conv_bf16_ok: multiples of 32)
-        wt = _weight_layout(weight, transpose, True, arith=3)
+    rows16 = feats.dtype != torch.float32        # (ConvolutionFunction hands fp32, bf16 or fp16 rows)
+    if rows16 and not L.load().u2mkd_conv_tiles_supported(feats.shape[1], cout, kmap.k):
+        # bf16 / fp16 storage, every shape the tile kernel has no instantiation for (_conv_rows16_ok: multiples of 32)
+        wt = _weight_layout(weight, transpose, True, arith=_arith16(feats.dtype))
         return kmap.pair_schedule().run(feats, wt, cout, bool(inverse) or bool(kflip), out)
-    if feats.dtype != torch.bfloat16 and _pairs_mode(feats.shape[1], cout, n_rows):
+    if not rows16 and _pairs_mode(feats.shape[1], cout, n_rows):
         x3 = _PAIRS_X3 and bool(L.load().u2mkd_conv_pairs_x3_supported(feats.shape[1], cout))
         f2 = x3 and _pairs_f16x2(feats.shape[1], cout)          # the same kernel in f16x2 arithmetic (arith-4 fragments)
         wt = _weight_layout(weight, transpose, x3, arith=4 if f2 else 0)
@@ -1022,7 +1066,7 @@ def _conv_os(feats, weight, transpose, cout, kmap, inverse, n_rows, kflip, epilo
 def conv_epilogue_supported(feats, cin, cout, k, n_rows):
     """True where conv_eval_affine can fold the affine into the convolution's store: fp32 rows on the tile-pair kernel
     (u2mkd_conv_forward_tiles_ep) or on the pair schedule (u2mkd_pairs_gather_sum_ep)."""
-    if feats.dtype != torch.float32 or bf16_rows() or cin % 4 or cout % 4:
+    if feats.dtype != torch.float32 or row_dtype() is not None or cin % 4 or cout % 4:
         return False
     if _pairs_mode(cin, cout, n_rows):
         return True
@@ -1131,7 +1175,8 @@ def invalidate_weight_caches(*_):
     _WEIGHT_EPOCH[1] += 1
 
 
-# Trainable weights whose MFMA-fragment images are live: (id(weight), slot) -> [weakref, slot, both, k, r, c, planes, data_ptr].
+# Trainable weights whose MFMA-fragment images are live: (id(weight), slot) -> [weakref, slot, both, k, r, c, planes, data_ptr,
+# fp16 plane (arith 5)]; the slot names the arith, so one weight used under bf16 and under fp16 autocast holds two jobs.
 # After an optimizer step ALL of them are re-laid by ONE launch (u2mkd_weight_fragments_batch) instead of one ~5 us
 # latency-bound launch per weight in front of its first convolution of the next step (~100 per KD step).
 _FRAG_JOBS = {}
@@ -1144,7 +1189,7 @@ def _register_fragments(weight, slot, both, k, r, c, arith):
         return
     if planes == 2 and arith != 4:
         return                     # (f32 fragments are 2 x 2 bytes per element too)
-    _FRAG_JOBS[(id(weight), slot)] = [weakref.ref(weight), slot, both, k, r, c, planes, weight.data_ptr()]
+    _FRAG_JOBS[(id(weight), slot)] = [weakref.ref(weight), slot, both, k, r, c, planes, weight.data_ptr(), int(arith == 5)]
     _FRAG_TABLE[0] = None
 
 
@@ -1169,8 +1214,8 @@ def refresh_weight_fragments(*_):
         return
     if _FRAG_TABLE[0] is None:
         rows, first = [], 0
-        for w, (_, _, both, k, r, c, planes, ptr) in live:
-            rows.append([ptr, both.data_ptr(), first, k, r, c, planes, 0])
+        for w, (_, _, both, k, r, c, planes, ptr, f16) in live:
+            rows.append([ptr, both.data_ptr(), first, k, r, c, planes, f16])
             first += 2 * (k * r * c // 512)
         # pinned staging + asynchronous copy: a pageable copy makes the host wait for everything queued on the stream --
         # right behind the optimizer that is the whole backward, i.e. the host's ~20 ms lead over the GPU
@@ -1191,8 +1236,8 @@ except ImportError:                                  # pragma: no cover -- torch
     pass
 
 
-def _conv_bf16_ok(cin, cout):
-    """channel counts the bf16-storage conv kernels take (tile kernel: 32..128; pair kernel: multiples of 32)"""
+def _conv_rows16_ok(cin, cout):
+    """channel counts the bf16- and fp16-storage conv kernels take (tile kernel: 32..128; pair kernel: multiples of 32)"""
     return cin >= 32 and cin % 32 == 0 and cout >= 32 and cout % 32 == 0
 
 
@@ -1218,8 +1263,9 @@ def _weight_layout(weight, transpose, fragments, arith=0):
             and weight.is_contiguous() and base.requires_grad == weight.requires_grad:
         holder, tag = base, ':%dx%dx%d' % (k, r, c)
     if fragments:
-        # arith 0 = the library's fp32-row arithmetic (bf16x3 / f32), 3 = ONE bf16 plane (bf16 storage), 4 = f16x2 (tile kernel)
-        slot = {3: '_u2mkd_wfrag3', 4: '_u2mkd_wfrag4'}.get(arith, '_u2mkd_wfrag') + tag
+        # arith 0 = the library's fp32-row arithmetic (bf16x3 / f32), 3 = ONE bf16 plane (bf16 storage), 4 = f16x2 (tile kernel),
+        # 5 = ONE fp16 plane (fp16 storage); a slot per arith: a module used under bf16 and then fp16 autocast keeps both images
+        slot = {3: '_u2mkd_wfrag3', 4: '_u2mkd_wfrag4', 5: '_u2mkd_wfrag5'}.get(arith, '_u2mkd_wfrag') + tag
         hit = holder.__dict__.get(slot)
         if hit is None or hit[0] != stamp:
             nbytes = L.load().u2mkd_weight_fragments_bytes(k, r, c, arith)
@@ -1283,7 +1329,7 @@ def _dense_x3_ok(cin, cout):
 def _dense_x3(x, weight, forward, bias=None, kernel_layout=False):
     """x @ weight.T (+ bias) (forward) or x @ weight (the input gradient) for nn.Linear's weight [out, in] on the
     bf16x3 pair kernel's dense mode; the fragment-order weights of both orientations come from one cached launch.
-    bf16 rows (bf16 storage): the same kernel's one-plane form, bf16 in and out, fp32 bias and accumulation.
+    bf16 / fp16 rows (16-bit storage): the same kernel's one-plane form, rows of that type in and out, fp32 bias and accumulation.
     ``kernel_layout``: ``weight`` is [in, out] (the one offset of a 1 x 1 x 1 spnn.Conv3d ``kernel``): x @ weight forward,
     x @ weight.T for the input gradient -- the other orientation of the same cached fragments, no transposed copy."""
     n = x.shape[0]
@@ -1291,11 +1337,11 @@ def _dense_x3(x, weight, forward, bias=None, kernel_layout=False):
         cout = weight.shape[-1] if forward else weight.shape[-2]
     else:
         cout = weight.shape[0] if forward else weight.shape[1]
-    b16 = x.dtype == torch.bfloat16
-    f2 = not b16 and _pairs_f16x2(x.shape[1], cout)
-    wf = _weight_layout(weight, forward if kernel_layout else not forward, True, arith=3 if b16 else (4 if f2 else 0))
+    rows16 = x.dtype != torch.float32
+    f2 = not rows16 and _pairs_f16x2(x.shape[1], cout)
+    wf = _weight_layout(weight, forward if kernel_layout else not forward, True, arith=_arith16(x.dtype) if rows16 else (4 if f2 else 0))
     y = torch.empty(n, cout, dtype=x.dtype, device=x.device)
-    L.call('u2mkd_linear_forward_bf16' if b16 else ('u2mkd_linear_forward_f16x2' if f2 else 'u2mkd_linear_forward_x3'), L.ptr(x), n,
+    L.call(_entry('u2mkd_linear_forward', x.dtype) if rows16 else ('u2mkd_linear_forward_f16x2' if f2 else 'u2mkd_linear_forward_x3'), L.ptr(x), n,
            x.shape[1], L.ptr(wf), cout, L.ptr(bias), L.ptr(y), L.stream())
     return y
 
@@ -1346,10 +1392,10 @@ class LinearFunction(Function):
         # the bias IS a leaf parameter (not a padded / cast copy): its gradient, too, is read by nobody before the backward ends
         ctx.bias_param = bias if (bias is not None and bias.is_leaf and bias.requires_grad and bias.dtype == torch.float32) else None
         ctx.overlap_ok = _deferred_overlap_ok()
-        want16 = bf16_rows()
-        b16 = want16 and _conv_bf16_ok(weight.shape[1], weight.shape[0])
+        want16 = row_dtype()
+        rows16 = want16 if _conv_rows16_ok(weight.shape[1], weight.shape[0]) else None
         ctx.in_dtype = x.dtype
-        x = _rows(x, b16)
+        x = _rows(x, rows16)
         if x.dim() != 2 or x.shape[1] != weight.shape[1]:
             raise RuntimeError(f'linear: input {tuple(x.shape)} does not match weight {tuple(weight.shape)}')
         if weight.shape[1] % 4 != 0 or weight.shape[0] % 4 != 0:
@@ -1360,15 +1406,14 @@ class LinearFunction(Function):
         if x.shape[0] == 0:
             return x.new_zeros(0, weight.shape[0])
         b = bias.contiguous().float() if bias is not None else None
-        ctx.x3 = b16 or _dense_x3_ok(weight.shape[1], weight.shape[0])
+        ctx.x3 = rows16 is not None or _dense_x3_ok(weight.shape[1], weight.shape[0])
         y = _dense_x3(x, weight, True, b) if ctx.x3 else _dense(x, weight, b)
-        return y.to(torch.bfloat16) if (want16 and not b16) else y
+        return y.to(want16) if (want16 is not None and rows16 is None) else y
 
     @staticmethod
     def backward(ctx, g):
         x, weight = ctx.saved_tensors
-        b16 = x.dtype == torch.bfloat16
-        g = _rows(g, b16)
+        g = _rows(g, x.dtype)
         n = x.shape[0]
         cout, cin = weight.shape
         gx = gw = gb = None
@@ -1384,7 +1429,7 @@ class LinearFunction(Function):
             gw = torch.empty_like(weight)
             side, deferred_join = _wgrad_side(ctx.weight_owner if ctx.weight_is_param else weight, ctx.weight_is_param, g.device,
                                                ctx.needs_input_grad[0], x, g, ws, gw, pairs, plan, allow=getattr(ctx, 'overlap_ok', True))
-            L.call('u2mkd_conv_wgrad_pairs_bf16' if b16 else 'u2mkd_conv_wgrad_pairs', L.ptr(g), cout, L.ptr(x), cin,
+            L.call(_entry('u2mkd_conv_wgrad_pairs', x.dtype), L.ptr(g), cout, L.ptr(x), cin,
                    L.ptr(pairs), L.ptr(plan), n, 1, 0, L.ptr(ws), nbytes, L.ptr(gw), side.cuda_stream if side is not None else L.stream())
         if ctx.needs_input_grad[0] and ctx.x3:
             gx = _dense_x3(g, weight, False)
@@ -1430,10 +1475,10 @@ class PointwiseConvFunction(Function):
         ctx.weight_is_param = kernel.is_leaf
         ctx.overlap_ok = _deferred_overlap_ok()
         cin, cout = kernel.shape[-2], kernel.shape[-1]
-        want16 = bf16_rows()
-        b16 = want16 and _conv_bf16_ok(cin, cout)
+        want16 = row_dtype()
+        rows16 = want16 if _conv_rows16_ok(cin, cout) else None
         ctx.in_dtype = x.dtype
-        x = _rows(x, b16)
+        x = _rows(x, rows16)
         if x.dim() != 2 or x.shape[1] != cin:
             raise RuntimeError(f'conv3d (1x1x1): input {tuple(x.shape)} does not match kernel {tuple(kernel.shape)}')
         ctx.save_for_backward(x, kernel)
@@ -1442,13 +1487,12 @@ class PointwiseConvFunction(Function):
             return x.new_zeros(0, cout)
         b = bias.contiguous().float() if bias is not None else None
         y = _dense_x3(x, kernel, True, b, kernel_layout=True)
-        return y.to(torch.bfloat16) if (want16 and not b16) else y
+        return y.to(want16) if (want16 is not None and rows16 is None) else y
 
     @staticmethod
     def backward(ctx, g):
         x, kernel = ctx.saved_tensors
-        b16 = x.dtype == torch.bfloat16
-        g = _rows(g, b16)
+        g = _rows(g, x.dtype)
         n = x.shape[0]
         cin, cout = kernel.shape[-2], kernel.shape[-1]
         gx = gw = gb = None
@@ -1462,7 +1506,7 @@ class PointwiseConvFunction(Function):
             gw = torch.empty_like(kernel)
             side, deferred_join = _wgrad_side(kernel, ctx.weight_is_param, g.device, ctx.needs_input_grad[0], x, g, ws, gw, pairs, plan,
                                                allow=getattr(ctx, 'overlap_ok', True))
-            L.call('u2mkd_conv_wgrad_pairs_bf16' if b16 else 'u2mkd_conv_wgrad_pairs', L.ptr(x), cin, L.ptr(g), cout,
+            L.call(_entry('u2mkd_conv_wgrad_pairs', x.dtype), L.ptr(x), cin, L.ptr(g), cout,
                    L.ptr(pairs), L.ptr(plan), n, 1, 0, L.ptr(ws), nbytes, L.ptr(gw), side.cuda_stream if side is not None else L.stream())
         if ctx.needs_input_grad[0]:
             gx = _dense_x3(g, kernel, False, kernel_layout=True)
@@ -1553,12 +1597,13 @@ class ConvolutionFunction(Function):
         ctx.weight_is_param = param.is_leaf and weight.data_ptr() == param.data_ptr() and weight.dtype == param.dtype
         ctx.overlap_ok = _deferred_overlap_ok()
         k, cin, cout = weight.shape
-        # bf16 storage (autocast to bfloat16): bf16 rows in and out, as torchsparse's custom_fwd(cast_inputs=half);
-        # shapes without a bf16 kernel (the 4-channel stem) compute on fp32 rows and round the result once
-        want16 = bf16_rows()
-        b16 = want16 and _conv_bf16_ok(cin, cout)
+        # 16-bit storage (autocast to bfloat16 or float16): rows of that type in and out, as torchsparse's
+        # custom_fwd(cast_inputs=half); shapes without a 16-bit kernel (the 4-channel stem) compute on fp32 rows and round the
+        # result once
+        want16 = row_dtype()
+        rows16 = want16 if _conv_rows16_ok(cin, cout) else None
         ctx.in_dtype = input.dtype
-        input = _rows(input, b16)
+        input = _rows(input, rows16)
         if input.shape[1] != cin:
             raise RuntimeError(f'conv3d: input has {input.shape[1]} channels, kernel expects {cin}')
         if cin % 4 != 0:
@@ -1575,14 +1620,13 @@ class ConvolutionFunction(Function):
         ctx.save_for_backward(input, weight)
         ctx.kmap = kmap
         ctx.transposed = transposed
-        return out.to(torch.bfloat16) if (want16 and not b16) else out
+        return out.to(want16) if (want16 is not None and rows16 is None) else out
 
     @staticmethod
     def backward(ctx, grad_output):
         input, weight = ctx.saved_tensors
         kmap, transposed = ctx.kmap, ctx.transposed
-        b16 = input.dtype == torch.bfloat16
-        g = _rows(grad_output, b16)
+        g = _rows(grad_output, input.dtype)
         k, cin, cout = weight.shape
         grad_input = grad_weight = None
         # The two gradients are independent: the weight gradient runs on a side stream next to
@@ -1601,7 +1645,7 @@ class ConvolutionFunction(Function):
             side, deferred_join = _wgrad_side(weight, ctx.weight_is_param, g.device, do_x, input, g, ws, grad_weight, pairs, plan,
                                                allow=getattr(ctx, 'overlap_ok', True))
             st = side.cuda_stream if side is not None else L.stream()
-            L.call('u2mkd_conv_wgrad_pairs_bf16' if b16 else 'u2mkd_conv_wgrad_pairs', L.ptr(input), cin, L.ptr(g), cout,
+            L.call(_entry('u2mkd_conv_wgrad_pairs', input.dtype), L.ptr(input), cin, L.ptr(g), cout,
                    L.ptr(pairs), L.ptr(plan), kmap.n_out, k, 1 if transposed else 0, L.ptr(ws), nbytes, L.ptr(grad_weight), st)
         if do_x:
             # dX[i] = sum_k dY[out_k(i)] @ W[k]^T : same kernel on the swapped-role table,
@@ -1690,19 +1734,19 @@ class BatchNormFunction(Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, running_mean, running_var, training, momentum, eps, relu, counter=None, res=None, stats=None):
         L.require_cuda(x)
-        # bf16 storage: rows stay bf16 through the BatchNorm (as nn.BatchNorm1d passes half through under the
+        # 16-bit storage: rows stay bf16 / fp16 through the BatchNorm (as nn.BatchNorm1d passes half through under the
         # reference's amp), statistics / parameters / gradient sums fp32
-        b16 = bf16_rows() or (x.dtype == torch.bfloat16 and _BF16_ROWS)
+        rows16 = row_dtype() or _stored16(x.dtype)
         ctx.in_dtype, ctx.res_dtype = x.dtype, (res.dtype if res is not None else None)
-        x = _rows(x, b16)
+        x = _rows(x, rows16)
         n, c = x.shape
         dev = x.device
         if res is not None:      # y = relu(bn(x) + res): the tail of a ResidualBlock in the same pass
             assert relu and res.shape == x.shape, (relu, res.shape, x.shape)
-            res = _rows(res, b16)
+            res = _rows(res, rows16)
         y = torch.empty_like(x)
         invstd = torch.empty(c, dtype=torch.float32, device=dev)
-        if training and stats is not None and not b16:
+        if training and stats is not None and rows16 is None:
             mean = torch.empty(c, dtype=torch.float32, device=dev)
             L.call('u2mkd_bn_train_forward_from_partial', L.ptr(x), L.ptr(res), n, c, L.ptr(gamma), L.ptr(beta), float(eps),
                    float(momentum), L.ptr(running_mean), L.ptr(running_var), L.ptr(counter), int(relu), L.ptr(stats.partial),
@@ -1711,12 +1755,12 @@ class BatchNormFunction(Function):
             slabs = L.load().u2mkd_bn_num_slabs(n)
             partial = torch.empty(max(slabs, 1) * 2 * c, dtype=torch.float32, device=dev)
             mean = torch.empty(c, dtype=torch.float32, device=dev)
-            L.call('u2mkd_bn_train_forward', L.ptr(x), L.ptr(res), int(b16), n, c, L.ptr(gamma), L.ptr(beta), float(eps),
+            L.call('u2mkd_bn_train_forward', L.ptr(x), L.ptr(res), _row_code(x.dtype), n, c, L.ptr(gamma), L.ptr(beta), float(eps),
                    float(momentum), L.ptr(running_mean), L.ptr(running_var), L.ptr(counter), int(relu), L.ptr(partial),
                    L.ptr(mean), L.ptr(invstd), L.ptr(y), L.stream())
         else:
             mean = running_mean
-            L.call('u2mkd_bn_eval_forward', L.ptr(x), L.ptr(res), int(b16), n, c, L.ptr(gamma), L.ptr(beta), float(eps),
+            L.call('u2mkd_bn_eval_forward', L.ptr(x), L.ptr(res), _row_code(x.dtype), n, c, L.ptr(gamma), L.ptr(beta), float(eps),
                    L.ptr(running_mean), L.ptr(running_var), int(relu), L.ptr(invstd), L.ptr(y), L.stream())
         ctx.save_for_backward(x, gamma, beta, mean, invstd, res)
         ctx.relu, ctx.training = bool(relu), bool(training)
@@ -1725,8 +1769,7 @@ class BatchNormFunction(Function):
     @staticmethod
     def backward(ctx, dy):
         x, gamma, beta, mean, invstd, res = ctx.saved_tensors
-        b16 = x.dtype == torch.bfloat16
-        dy = _rows(dy, b16)
+        dy = _rows(dy, x.dtype)
         n, c = x.shape
         dev = x.device
         slabs = L.load().u2mkd_bn_num_slabs(n)
@@ -1735,7 +1778,7 @@ class BatchNormFunction(Function):
         dbeta = torch.empty(c, dtype=torch.float32, device=dev)
         dx = torch.empty_like(x)
         dres = torch.empty_like(x) if res is not None else None
-        L.call('u2mkd_bn_backward', L.ptr(dy), L.ptr(x), L.ptr(res), int(b16), n, c, L.ptr(mean), L.ptr(invstd), L.ptr(gamma),
+        L.call('u2mkd_bn_backward', L.ptr(dy), L.ptr(x), L.ptr(res), _row_code(x.dtype), n, c, L.ptr(mean), L.ptr(invstd), L.ptr(gamma),
                L.ptr(beta), int(ctx.relu), int(ctx.training), L.ptr(partial), L.ptr(dgamma), L.ptr(dbeta), L.ptr(dx),
                L.ptr(dres), L.stream())
         if dx.dtype != ctx.in_dtype:
@@ -1794,19 +1837,19 @@ class SyncBatchNormFunction(Function):
     def forward(ctx, x, gamma, beta, running_mean, running_var, momentum, eps, relu, group, world, res=None, counter=None):
         import torch.distributed as dist
         L.require_cuda(x)
-        b16 = bf16_rows() or (x.dtype == torch.bfloat16 and _BF16_ROWS)
+        rows16 = row_dtype() or _stored16(x.dtype)
         ctx.in_dtype = x.dtype
-        x = _rows(x, b16)
+        x = _rows(x, rows16)
         if res is not None:          # relu(bn(x) + res): the tail of a ResidualBlock inside the apply pass
             ctx.res_dtype = res.dtype
-            res = _rows(res, b16)
+            res = _rows(res, rows16)
         n, c = x.shape
         dev = x.device
         st = L.stream()
         slabs = L.load().u2mkd_bn_num_slabs(n)
         partial = torch.empty(max(slabs, 1) * 2 * c, dtype=torch.float32, device=dev)
         stats = torch.empty(2 * c + 1, dtype=torch.float32, device=dev)
-        L.call('u2mkd_bn_local_stats', L.ptr(x), int(b16), n, c, L.ptr(partial), L.ptr(stats), st)
+        L.call('u2mkd_bn_local_stats', L.ptr(x), _row_code(x.dtype), n, c, L.ptr(partial), L.ptr(stats), st)
         note_collective('all_gather', stats)
         if world > 1:
             gathered = torch.empty(world, 2 * c + 1, dtype=torch.float32, device=dev)
@@ -1819,7 +1862,7 @@ class SyncBatchNormFunction(Function):
         L.call('u2mkd_bn_merge_stats', L.ptr(gathered), world, c, float(eps), float(momentum), L.ptr(running_mean),
                L.ptr(running_var), L.ptr(mean), L.ptr(invstd), L.ptr(total), L.ptr(counter), L.stream())
         y = torch.empty_like(x)
-        L.call('u2mkd_bn_apply', L.ptr(x), L.ptr(res), int(b16), n, c, L.ptr(mean), L.ptr(invstd), L.ptr(gamma), L.ptr(beta),
+        L.call('u2mkd_bn_apply', L.ptr(x), L.ptr(res), _row_code(x.dtype), n, c, L.ptr(mean), L.ptr(invstd), L.ptr(gamma), L.ptr(beta),
                int(relu), L.ptr(y), L.stream())
         ctx.save_for_backward(x, gamma, beta, mean, invstd, total, res)
         ctx.relu, ctx.group, ctx.world = bool(relu), group, world
@@ -1829,8 +1872,7 @@ class SyncBatchNormFunction(Function):
     def backward(ctx, dy):
         import torch.distributed as dist
         x, gamma, beta, mean, invstd, total, res = ctx.saved_tensors
-        b16 = x.dtype == torch.bfloat16
-        dy = _rows(dy, b16)
+        dy = _rows(dy, x.dtype)
         n, c = x.shape
         dev = x.device
         slabs = L.load().u2mkd_bn_num_slabs(n)
@@ -1839,14 +1881,14 @@ class SyncBatchNormFunction(Function):
         # DDP averages them)
         both = torch.empty(2, 2 * c, dtype=torch.float32, device=dev)
         sums, local = both[0], both[1]
-        L.call('u2mkd_bn_backward_local', L.ptr(dy), L.ptr(x), L.ptr(res), int(b16), n, c, L.ptr(mean), L.ptr(invstd),
+        L.call('u2mkd_bn_backward_local', L.ptr(dy), L.ptr(x), L.ptr(res), _row_code(x.dtype), n, c, L.ptr(mean), L.ptr(invstd),
                L.ptr(gamma), L.ptr(beta), int(ctx.relu), L.ptr(partial), L.ptr(sums), L.ptr(local), L.stream())
         note_collective('all_reduce', sums)
         if ctx.world > 1:
             _sum_over_ranks(sums, ctx.group)
         dx = torch.empty_like(x)
         dres = torch.empty_like(x) if res is not None else None
-        L.call('u2mkd_bn_backward_apply', L.ptr(dy), L.ptr(x), L.ptr(res), int(b16), n, c, L.ptr(total), L.ptr(mean),
+        L.call('u2mkd_bn_backward_apply', L.ptr(dy), L.ptr(x), L.ptr(res), _row_code(x.dtype), n, c, L.ptr(total), L.ptr(mean),
                L.ptr(invstd), L.ptr(gamma), L.ptr(beta), int(ctx.relu), L.ptr(sums), L.ptr(dx), L.ptr(dres), L.stream())
         if dres is not None and dres.dtype != ctx.res_dtype:
             dres = dres.to(ctx.res_dtype)
@@ -1903,13 +1945,13 @@ def batch_norm(x: torch.Tensor, bn: torch.nn.modules.batchnorm._BatchNorm, relu:
         return y
     if training and x.shape[0] < 2:
         raise ValueError(f'Expected more than 1 value per channel when training, got input size {tuple(x.shape)}')
-    if stats is not None and training and stats.describes(x) and not bf16_rows() and (residual is None or residual.dtype == torch.float32):
+    if stats is not None and training and stats.describes(x) and row_dtype() is None and (residual is None or residual.dtype == torch.float32):
         # the slab statistics came with x (the producing convolution's store): merge + apply, no statistics pass
         y = BatchNormFunction.apply(x, bn.weight, bn.bias, rm, rv, training, factor, bn.eps, relu, counter, residual, stats)
         torch._C._increment_version(written)
         return y
     h = _HOST if _HOST is not False else host_ops()
-    if h is not None and x.dtype == torch.float32 and x.is_cuda and x.shape[0] > 0 and not bf16_rows() \
+    if h is not None and x.dtype == torch.float32 and x.is_cuda and x.shape[0] > 0 and row_dtype() is None \
             and (residual is None or residual.dtype == torch.float32):
         # the same pass with its host side in C++ (csrc_host/host_ops.cpp: BatchNormRows)
         return h.batch_norm_rows(x, bn.weight, bn.bias, rm, rv, training, factor, bn.eps, relu, counter, residual)

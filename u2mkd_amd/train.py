@@ -86,9 +86,13 @@ class _Amp:
     """``amp.autocast(enabled)`` + ``amp.GradScaler(enabled)`` of the reference trainers
     (core/nusc_trainers.py:157-158,285,362-364; core/spformer_trainer.py likewise).  amp = False / None: fp32
     (the parity path); 'fp16': the reference's mode (autocast to half + loss scaling); 'bf16': autocast to
-    bfloat16, no loss scaling needed (fp32 exponent range) -- BASELINE.json configs[4].  The sparse operators
-    of this package take fp32 rows (like torchsparse's fp32-only CPU backend, they up-cast their inputs), so
-    under autocast the dense torch.nn layers -- the SwiftNet-18 camera branch above all -- run reduced."""
+    bfloat16, no loss scaling needed (fp32 exponent range) -- BASELINE.json configs[4].  In both reduced modes the
+    sparse operators of this package keep their feature rows in the autocast dtype between them, as torchsparse's
+    ``custom_fwd(cast_inputs=torch.half)`` does (torchsparse/nn/functional.py: ``row_dtype``): convolutions, Linear,
+    BatchNorm, voxelize and devoxelize read and write fp16 / bf16 rows, while accumulations, BatchNorm statistics, master
+    weights and every parameter gradient stay fp32.  An fp16 row value beyond +-65504 is stored as inf and reaches the
+    gradients, which is how the GradScaler finds the steps to skip.  U2MKD_F16_ROWS=0 / U2MKD_BF16_ROWS=0 give fp32 rows
+    under the respective autocast (only the dense torch.nn layers run reduced then)."""
 
     def __init__(self, amp):
         if amp is True:
