@@ -859,6 +859,20 @@ int u2mkd_sptr_attention_forward_tiles(const float *q, const float *k, const flo
 int32_t u2mkd_sgd_chunk_elements(void);
 int u2mkd_sgd_batch(const int64_t *jobs, int32_t n_jobs, int64_t total_chunks, float lr, float momentum, float weight_decay,
                     int32_t nesterov, int32_t contract, u2mkd_stream_t s);
+/* The same update driven by a torch.amp.GradScaler (torch/amp/grad_scaler.py), over the same job table, with the scaler's
+ * scalars read on the device (one float each) -- no host read decides the step.
+ * u2mkd_grads_unscale_check = torch._amp_foreach_non_finite_check_and_unscale_ over all gradients of a group in one launch:
+ * g *= *inv_scale in place (nothing is stored when *inv_scale == 1: check only), *found_inf = 1.0f where a product is not
+ * finite (a plain store; never cleared here); jobs without a gradient are skipped.  torch flags the loaded value instead of
+ * the product: same stored values, and the same flag except for a finite gradient that overflows in the multiply (inverse
+ * scale above 1), which is flagged here.
+ * u2mkd_sgd_batch_amp = u2mkd_sgd_batch with found_inf (required): *found_inf != 0 -> no parameter, momentum buffer or
+ * gradient is written; grad_scale (or NULL): every gradient is first multiplied by (float)(1.0 / (double)*grad_scale), the
+ * value GradScaler.unscale_ computes, and stored back to the gradient, as torch's fused optimizers do. */
+int u2mkd_grads_unscale_check(const int64_t *jobs, int32_t n_jobs, int64_t total_chunks, const float *inv_scale, float *found_inf,
+                              u2mkd_stream_t s);
+int u2mkd_sgd_batch_amp(const int64_t *jobs, int32_t n_jobs, int64_t total_chunks, float lr, float momentum, float weight_decay,
+                        int32_t nesterov, int32_t contract, const float *grad_scale, const float *found_inf, u2mkd_stream_t s);
 
 #ifdef __cplusplus
 }

@@ -13,7 +13,7 @@ from . import distributed as D
 from . import kd as KD
 from . import torchsparse as ts
 from .losses import MixLovaszCrossEntropy
-from .optim import FusedSGD
+from .optim import FusedSGD, GradScaler
 
 __all__ = ['cosine_schedule_with_warmup', 'make_optimizer', 'LidarStep', 'KDStep', 'TeacherWatch', 'kd_batch_to_device', 'pin_kd_batch', 'fresh_batch', 'state_dict',
            'load_state_dict', 'load_weights']
@@ -101,7 +101,7 @@ class _Amp:
             raise ValueError(f'amp must be False, "fp16" or "bf16", got {amp!r}')
         self.dtype = {'fp16': torch.float16, 'bf16': torch.bfloat16}.get(amp)
         self.enabled = self.dtype is not None
-        self.scaler = torch.amp.GradScaler('cuda', enabled=(amp == 'fp16'))
+        self.scaler = GradScaler('cuda', enabled=(amp == 'fp16'))      # (torch.amp.GradScaler; its check over FusedSGD's gradients is one launch)
 
     def autocast(self):
         return torch.autocast('cuda', dtype=self.dtype or torch.float16, enabled=self.enabled)
