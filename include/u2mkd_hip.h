@@ -723,6 +723,9 @@ int u2mkd_sptr_attention_backward_strided(const float *q, const float *k, const 
                                           int64_t n, int32_t h, int32_t hdim, float *delta /*[n,h] scratch*/,
                                           void *workspace, size_t workspace_bytes, float *dq, float *dk, float *dv,
                                           int64_t ld_grad, float *dtq, float *dtk, float *dtv, u2mkd_stream_t s);
+/* The two strided entries on 16-BIT ROWS (u2mkd_sptr_attention_{forward,backward}_strided_bf16 / _f16) are declared in
+ * u2mkd_hip_sptr_rows16.h, which this header includes here: they are part of this ABI.                                 */
+#include "u2mkd_hip_sptr_rows16.h"
 
 /* dtq = dtk = dtv = NULL in the two backward entries: the slab sum (their last launch) is left to the caller --
  * u2mkd_sptr_table_reduce(workspace, the same n, h, L, split_a, ...) on any stream ordered behind the backward call.  The

@@ -181,6 +181,12 @@ SIGNATURES = {
     'u2mkd_ti_weights': (C.c_int, [_p, _p, _i64, _f32, _p, _p, _p]),
 }
 
+# the window attention's strided entries on 16-bit rows (q, k, v, out, dout, dq, dk, dv: bf16 / fp16, strides in elements), declared in
+# include/u2mkd_hip_sptr_rows16.h: the arguments of the fp32 entries above
+SPTR_ROWS16_SIGNATURES = {
+    name + sfx: SIGNATURES[name]
+    for name in ('u2mkd_sptr_attention_forward_strided', 'u2mkd_sptr_attention_backward_strided') for sfx in ('_bf16', '_f16')}
+
 _lib = None
 _raw_stream = torch._C._cuda_getCurrentRawStream
 _current_device = torch._C._cuda_getDevice
@@ -196,7 +202,7 @@ def load():
             f'{LIB_PATH} is missing: build it with `python -m u2mkd_amd.build` '
             '(u2mkd_amd has no CPU or PyTorch fallback path)')
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(SPTR_ROWS16_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -213,21 +213,49 @@ __device__ __forceinline__ void tab_sum(const float *tab, const int r[3], float 
     }
 }
 
-__device__ __forceinline__ void load16(const float *p, float out[kHd]) {
+// ---- the row type T of q, k, v, out, dout and dq, dk, dv: float, bf16row or _Float16 (common.h) ----------------------
+// T enters at the loads of a (token, head) row (load16) and at the stores of one (store16 / st4), nowhere else: a 16-bit
+// value is widened exactly in a register (the number .float() gives), everything between -- q_scale, the table sums, the
+// online softmax, lse, delta, the histogram strips, the MFMA contraction, the slabs -- is the same fp32 code for every T,
+// and a result is rounded to nearest-even ONCE at its store (fp16: beyond +-65504 -> inf, never saturated).  A 16-bit row
+// is 32 bytes: the entries require 16-byte aligned rows, so its four ld4 / st4 are two 16-byte accesses.
+template <typename T>
+__device__ __forceinline__ void load16(const T *p, float out[kHd]) {
+    if constexpr (sizeof(T) == 2) p = static_cast<const T *>(__builtin_assume_aligned(p, 16));
 #pragma unroll
     for (int v = 0; v < 4; ++v) {
-        float4 x = reinterpret_cast<const float4 *>(p)[v];
+        float4 x = ld4<T>(p, v);
         out[4 * v] = x.x; out[4 * v + 1] = x.y; out[4 * v + 2] = x.z; out[4 * v + 3] = x.w;
     }
 }
 
+// A product that goes straight to a 16-bit store: the value rounded to 16 bits is the fp32 PRODUCT (rounded to fp32), the number
+// the fp32 kernels store and a later cast rounds.  Left to instruction selection, fp16 gets v_fma_mixlo_f16 / _mixhi_f16, which
+// round the exact product once: the last place of ~1 stored value in 10^4 differed from the fp32 kernel's (MI355X,
+// tests/test_gpu_sptr_rows16.py).  The empty asm pins the fp32 value in a register; fp32 rows: the identity.  Used where the
+// fusion happens -- the one-lane-per-token kernels (sptr_attn_fwd_kernel's out, sptr_bwd_query_kernel<T, 1>'s dq); the
+// S > 1 forms convert with v_cvt_pk and are left as the compiler schedules them.
+template <typename T>
+__device__ __forceinline__ float product32(float x) {
+    if constexpr (sizeof(T) == 2) asm("" : "+v"(x));
+    return x;
+}
+
+template <typename T>
+__device__ __forceinline__ void store16(T *p, const float x[kHd]) {
+    if constexpr (sizeof(T) == 2) p = static_cast<T *>(__builtin_assume_aligned(p, 16));
+#pragma unroll
+    for (int v = 0; v < 4; ++v) st4<T>(p, v, make_float4(x[4 * v], x[4 * v + 1], x[4 * v + 2], x[4 * v + 3]));
+}
+
 // ---- forward: out[t,h,:] = softmax_j(s) . (v_j + Tv(rel)),  lse saved per (sorted pos, head)
+template <typename T>
 __global__ void __launch_bounds__(kSptrThreads)
-sptr_attn_fwd_kernel(const float *__restrict__ q, const float *__restrict__ k, const float *__restrict__ v,
+sptr_attn_fwd_kernel(const T *__restrict__ q, const T *__restrict__ k, const T *__restrict__ v,
                      const int32_t *__restrict__ sort_idx, const int32_t *__restrict__ wstart,
                      const int32_t *__restrict__ wlen, const int32_t *__restrict__ qc,
                      const float *__restrict__ radial, const float *__restrict__ tq, const float *__restrict__ tk,
-                     const float *__restrict__ tv, int L, RelCtx rc, int64_t n, int h, float *__restrict__ out,
+                     const float *__restrict__ tv, int L, RelCtx rc, int64_t n, int h, T *__restrict__ out,
                      float *__restrict__ lse, SptrLayout ly) {
     extern __shared__ __attribute__((aligned(16))) float s_tab[];
     const int hh = blockIdx.y;
@@ -275,11 +303,12 @@ sptr_attn_fwd_kernel(const float *__restrict__ q, const float *__restrict__ k, c
         m = mn;
     }
     float inv = 1.f / l;
-    float *o = out + t * (size_t)ly.ld_out + hh * kHd;
+    T *o = out + t * (size_t)ly.ld_out + hh * kHd;
+    if constexpr (sizeof(T) == 2) o = static_cast<T *>(__builtin_assume_aligned(o, 16));
 #pragma unroll
     for (int v4 = 0; v4 < 4; ++v4)
-        reinterpret_cast<float4 *>(o)[v4] =
-            make_float4(acc[4 * v4] * inv, acc[4 * v4 + 1] * inv, acc[4 * v4 + 2] * inv, acc[4 * v4 + 3] * inv);
+        st4<T>(o, v4, make_float4(product32<T>(acc[4 * v4] * inv), product32<T>(acc[4 * v4 + 1] * inv),
+                                  product32<T>(acc[4 * v4 + 2] * inv), product32<T>(acc[4 * v4 + 3] * inv)));
     lse[p * h + hh] = m + __logf(l);
 }
 
@@ -291,13 +320,13 @@ sptr_attn_fwd_kernel(const float *__restrict__ q, const float *__restrict__ k, c
 // Here S consecutive lanes share a token: lane s walks keys s, s + S, ... with its own online-softmax state, and the
 // states are merged by a butterfly over the S lanes (a fixed tree: deterministic; every lane ends with the same
 // value).  S x more waves hide the latency and the longest chain is S x shorter.
-template <int S>
+template <typename T, int S>
 __global__ void __launch_bounds__(kSptrThreads)
-sptr_attn_fwd_split_kernel(const float *__restrict__ q, const float *__restrict__ k, const float *__restrict__ v,
+sptr_attn_fwd_split_kernel(const T *__restrict__ q, const T *__restrict__ k, const T *__restrict__ v,
                            const int32_t *__restrict__ sort_idx, const int32_t *__restrict__ wstart,
                            const int32_t *__restrict__ wlen, const int32_t *__restrict__ qc,
                            const float *__restrict__ radial, const float *__restrict__ tq, const float *__restrict__ tk,
-                           const float *__restrict__ tv, int L, RelCtx rc, int64_t n, int h, float *__restrict__ out,
+                           const float *__restrict__ tv, int L, RelCtx rc, int64_t n, int h, T *__restrict__ out,
                            float *__restrict__ lse, SptrLayout ly) {
     extern __shared__ __attribute__((aligned(16))) float s_tab[];
     static_assert(S >= 2 && S <= 16 && (S & (S - 1)) == 0, "lanes per token: 2, 4, 8 or 16");
@@ -361,17 +390,18 @@ sptr_attn_fwd_split_kernel(const float *__restrict__ q, const float *__restrict_
     }
     if (live && sub == 0) {
         const float inv = 1.f / l;
-        float *o = out + t * (size_t)ly.ld_out + hh * kHd;
+        T *o = out + t * (size_t)ly.ld_out + hh * kHd;
+        if constexpr (sizeof(T) == 2) o = static_cast<T *>(__builtin_assume_aligned(o, 16));
 #pragma unroll
         for (int v4 = 0; v4 < 4; ++v4)
-            reinterpret_cast<float4 *>(o)[v4] =
-                make_float4(acc[4 * v4] * inv, acc[4 * v4 + 1] * inv, acc[4 * v4 + 2] * inv, acc[4 * v4 + 3] * inv);
+            st4<T>(o, v4, make_float4(acc[4 * v4] * inv, acc[4 * v4 + 1] * inv, acc[4 * v4 + 2] * inv, acc[4 * v4 + 3] * inv));
         lse[p * h + hh] = m + __logf(l);
     }
 }
 
 // delta[p,h] = sum_d dout[t,h,d] * out[t,h,d]
-__global__ void sptr_delta_kernel(const float *__restrict__ dout, const float *__restrict__ out,
+template <typename T>
+__global__ void sptr_delta_kernel(const T *__restrict__ dout, const T *__restrict__ out,
                                   const int32_t *__restrict__ sort_idx, int64_t n, int h, float *__restrict__ delta,
                                   int64_t ld_out) {
     int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -379,10 +409,18 @@ __global__ void sptr_delta_kernel(const float *__restrict__ dout, const float *_
     int64_t p = e / h;
     int hh = (int)(e - p * h);
     int64_t t = sort_idx[p];
-    const float *a = dout + t * ld_out + hh * kHd, *b = out + t * ld_out + hh * kHd;
     float s = 0.f;
+    if constexpr (sizeof(T) == 4) {
+        const float *a = dout + t * ld_out + hh * kHd, *b = out + t * ld_out + hh * kHd;
 #pragma unroll
-    for (int d = 0; d < kHd; ++d) s += a[d] * b[d];
+        for (int d = 0; d < kHd; ++d) s += a[d] * b[d];
+    } else {
+        float a[kHd], b[kHd];
+        load16(dout + t * ld_out + hh * kHd, a);
+        load16(out + t * ld_out + hh * kHd, b);
+#pragma unroll
+        for (int d = 0; d < kHd; ++d) s += a[d] * b[d];
+    }
     delta[e] = s;
 }
 
@@ -469,14 +507,14 @@ __device__ __forceinline__ void hist_store_slab(float *slab, const int (&table_o
 // gradients are summed by a butterfly.  A workgroup then holds 128 / S tokens: S x fewer strips, more workgroups per
 // CU, S x shorter chains.
 // query role: dq_i, and the Tq / Tv table gradients
-template <int S>
+template <typename T, int S>
 __device__ __forceinline__ void
-sptr_bwd_query_body(const float *__restrict__ q, const float *__restrict__ k, const float *__restrict__ v,
-                      const float *__restrict__ dout, const float *__restrict__ lse, const float *__restrict__ delta,
+sptr_bwd_query_body(const T *__restrict__ q, const T *__restrict__ k, const T *__restrict__ v,
+                      const T *__restrict__ dout, const float *__restrict__ lse, const float *__restrict__ delta,
                       const int32_t *__restrict__ sort_idx, const int32_t *__restrict__ wstart,
                       const int32_t *__restrict__ wlen, const int32_t *__restrict__ qc,
                       const float *__restrict__ radial, const float *__restrict__ tq, const float *__restrict__ tk,
-                      const float *__restrict__ tv, int L, RelCtx rc, int64_t n, int h, float *__restrict__ dq,
+                      const float *__restrict__ tv, int L, RelCtx rc, int64_t n, int h, T *__restrict__ dq,
                       float *__restrict__ slabs, SptrLayout ly) {
     extern __shared__ __attribute__((aligned(16))) float s_tab[];
     constexpr int NT = 2, HS = NT * kHistTab + 1, TPB = kSptrThreads / S, TW = 64 / S;
@@ -590,9 +628,15 @@ sptr_bwd_query_body(const float *__restrict__ q, const float *__restrict__ k, co
 #pragma unroll
                 for (int d = 0; d < kHd; ++d) dqi[d] += __shfl_xor(dqi[d], off);
             if (sub == 0) {
-                float *o1 = dq + t * (size_t)ly.ld_grad + hh * kHd;      // d(unscaled q) = q_scale * d(q)
+                T *o1 = dq + t * (size_t)ly.ld_grad + hh * kHd;          // d(unscaled q) = q_scale * d(q)
+                if constexpr (sizeof(T) == 4) {
 #pragma unroll
-                for (int d = 0; d < kHd; ++d) o1[d] = dqi[d] * ly.q_scale;
+                    for (int d = 0; d < kHd; ++d) o1[d] = dqi[d] * ly.q_scale;
+                } else {
+#pragma unroll
+                    for (int d = 0; d < kHd; ++d) dqi[d] = S == 1 ? product32<T>(dqi[d] * ly.q_scale) : dqi[d] * ly.q_scale;
+                    store16(o1, dqi);
+                }
             }
         }
         if (sub == 0) {
@@ -615,15 +659,15 @@ sptr_bwd_query_body(const float *__restrict__ q, const float *__restrict__ k, co
 }
 
 // key role: dk_j, dv_j and the Tk table gradient
-template <int S>
+template <typename T, int S>
 __device__ __forceinline__ void
-sptr_bwd_key_body(const float *__restrict__ q, const float *__restrict__ k, const float *__restrict__ v,
-                    const float *__restrict__ dout, const float *__restrict__ lse, const float *__restrict__ delta,
+sptr_bwd_key_body(const T *__restrict__ q, const T *__restrict__ k, const T *__restrict__ v,
+                    const T *__restrict__ dout, const float *__restrict__ lse, const float *__restrict__ delta,
                     const int32_t *__restrict__ sort_idx, const int32_t *__restrict__ wstart,
                     const int32_t *__restrict__ wlen, const int32_t *__restrict__ qc,
                     const float *__restrict__ radial, const float *__restrict__ tq, const float *__restrict__ tk,
-                    const float *__restrict__ tv, int L, RelCtx rc, int64_t n, int h, float *__restrict__ dk,
-                    float *__restrict__ dv, float *__restrict__ slabs, SptrLayout ly) {
+                    const float *__restrict__ tv, int L, RelCtx rc, int64_t n, int h, T *__restrict__ dk,
+                    T *__restrict__ dv, float *__restrict__ slabs, SptrLayout ly) {
     extern __shared__ __attribute__((aligned(16))) float s_tab[];
     constexpr int NT = 1, HS = NT * kHistTab + 1, TPB = kSptrThreads / S, TW = 64 / S;
     const int hh = blockIdx.y;
@@ -736,9 +780,14 @@ sptr_bwd_key_body(const float *__restrict__ q, const float *__restrict__ k, cons
                     dvi[d] += __shfl_xor(dvi[d], off);
                 }
             if (sub == 0) {
-                float *o2 = dk + t * (size_t)ly.ld_grad + hh * kHd, *o3 = dv + t * (size_t)ly.ld_grad + hh * kHd;
+                T *o2 = dk + t * (size_t)ly.ld_grad + hh * kHd, *o3 = dv + t * (size_t)ly.ld_grad + hh * kHd;
+                if constexpr (sizeof(T) == 4) {
 #pragma unroll
-                for (int d = 0; d < kHd; ++d) { o2[d] = dki[d]; o3[d] = dvi[d]; }
+                    for (int d = 0; d < kHd; ++d) { o2[d] = dki[d]; o3[d] = dvi[d]; }
+                } else {
+                    store16(o2, dki);
+                    store16(o3, dvi);
+                }
             }
         }
         if (sub == 0) {
@@ -767,35 +816,35 @@ sptr_bwd_key_body(const float *__restrict__ q, const float *__restrict__ k, cons
 #define U2_SPTR_BWD_BOUNDS __launch_bounds__(kSptrThreads, (S == 16 ? 2 : 1))
 #endif
 #define U2_SPTR_BWD_IN                                                                                                   \
-    const float *__restrict__ q, const float *__restrict__ k, const float *__restrict__ v, const float *__restrict__ dout,  \
+    const T *__restrict__ q, const T *__restrict__ k, const T *__restrict__ v, const T *__restrict__ dout,                  \
         const float *__restrict__ lse, const float *__restrict__ delta, const int32_t *__restrict__ sort_idx,             \
         const int32_t *__restrict__ wstart, const int32_t *__restrict__ wlen, const int32_t *__restrict__ qc,             \
         const float *__restrict__ radial, const float *__restrict__ tq, const float *__restrict__ tk,                     \
         const float *__restrict__ tv, int L, RelCtx rc, int64_t n, int h
 #define U2_SPTR_BWD_PASS q, k, v, dout, lse, delta, sort_idx, wstart, wlen, qc, radial, tq, tk, tv, L, rc, n, h
 
-template <int S>
+template <typename T, int S>
 __global__ void U2_SPTR_BWD_BOUNDS
-sptr_bwd_query_kernel(U2_SPTR_BWD_IN, float *__restrict__ dq, float *__restrict__ slabs, SptrLayout ly) {
-    sptr_bwd_query_body<S>(U2_SPTR_BWD_PASS, dq, slabs, ly);
+sptr_bwd_query_kernel(U2_SPTR_BWD_IN, T *__restrict__ dq, float *__restrict__ slabs, SptrLayout ly) {
+    sptr_bwd_query_body<T, S>(U2_SPTR_BWD_PASS, dq, slabs, ly);
 }
 
-template <int S>
+template <typename T, int S>
 __global__ void U2_SPTR_BWD_BOUNDS
-sptr_bwd_key_kernel(U2_SPTR_BWD_IN, float *__restrict__ dk, float *__restrict__ dv, float *__restrict__ slabs, SptrLayout ly) {
-    sptr_bwd_key_body<S>(U2_SPTR_BWD_PASS, dk, dv, slabs, ly);
+sptr_bwd_key_kernel(U2_SPTR_BWD_IN, T *__restrict__ dk, T *__restrict__ dv, float *__restrict__ slabs, SptrLayout ly) {
+    sptr_bwd_key_body<T, S>(U2_SPTR_BWD_PASS, dk, dv, slabs, ly);
 }
 
 // Both roles in ONE launch, grid (G, heads, 2): blockIdx.z = 0 the query role, 1 the key role.  The two are independent (they
 // write different rows of the gradients and different tables of the same per-wave slab), and with S > 1 lanes per token
 // (the spherical branch at the coarse strides: 128 workgroups x heads of 2 waves, ~40 KB of LDS each) one role alone leaves
 // most of the chip idle: launched one behind the other they were the longest kernels of the student's backward chain.
-template <int S>
+template <typename T, int S>
 __global__ void U2_SPTR_BWD_BOUNDS
-sptr_bwd_both_kernel(U2_SPTR_BWD_IN, float *__restrict__ dq, float *__restrict__ dk, float *__restrict__ dv,
+sptr_bwd_both_kernel(U2_SPTR_BWD_IN, T *__restrict__ dq, T *__restrict__ dk, T *__restrict__ dv,
                      float *__restrict__ slabs, SptrLayout ly) {
-    if (blockIdx.z == 0) sptr_bwd_query_body<S>(U2_SPTR_BWD_PASS, dq, slabs, ly);
-    else sptr_bwd_key_body<S>(U2_SPTR_BWD_PASS, dk, dv, slabs, ly);
+    if (blockIdx.z == 0) sptr_bwd_query_body<T, S>(U2_SPTR_BWD_PASS, dq, slabs, ly);
+    else sptr_bwd_key_body<T, S>(U2_SPTR_BWD_PASS, dk, dv, slabs, ly);
 }
 #undef U2_SPTR_BWD_IN
 #undef U2_SPTR_BWD_PASS
@@ -899,26 +948,39 @@ static int sptr_check(const char *who, int64_t n, int h, int hdim, int L, int qg
     return 0;
 }
 
-int u2mkd_sptr_attention_forward_strided(const float *q, const float *k, const float *v, int64_t ld_qkv, float q_scale,
-                                         const int32_t *sort_idx, const int32_t *wstart, const int32_t *wlen,
-                                         const int32_t *qc, const float *radial, const float *tq, const float *tk,
-                                         const float *tv, int32_t L, int32_t qgl, float split_a, int64_t n, int32_t h,
-                                         int32_t hdim, float *out, int64_t ld_out, float *lse, u2mkd_stream_t s) {
+}  // extern "C"
+
+// 16-bit rows (T = bf16row / _Float16) move as 16-byte accesses: every row pointer 16-byte aligned, every stride (in
+// elements) a multiple of 8.  (fp32 rows: strides in multiples of 4 floats, as before.)
+template <typename T> constexpr int kRowVec = 16 / (int)sizeof(T);
+static bool sptr_aligned16(std::initializer_list<const void *> ps) {
+    for (const void *p : ps)
+        if (reinterpret_cast<uintptr_t>(p) % 16) return false;
+    return true;
+}
+
+template <typename T>
+static int sptr_forward_strided(const T *q, const T *k, const T *v, int64_t ld_qkv, float q_scale, const int32_t *sort_idx,
+                                const int32_t *wstart, const int32_t *wlen, const int32_t *qc, const float *radial,
+                                const float *tq, const float *tk, const float *tv, int32_t L, int32_t qgl, float split_a,
+                                int64_t n, int32_t h, int32_t hdim, T *out, int64_t ld_out, float *lse, u2mkd_stream_t s) {
     if (n == 0 || h == 0) return 0;
     U2_REQUIRE(q && k && v && sort_idx && wstart && wlen && qc && tq && tk && tv && out && lse,
                "u2mkd_sptr_attention_forward: null pointer");
     if (int rc = sptr_check("u2mkd_sptr_attention_forward", n, h, hdim, L, qgl, split_a)) return rc;
     U2_REQUIRE(split_a <= 0.f || radial, "u2mkd_sptr_attention_forward: spherical branch needs the radial coordinate");
-    U2_REQUIRE(ld_qkv >= (int64_t)h * kHd && ld_out >= (int64_t)h * kHd && ld_qkv % 4 == 0 && ld_out % 4 == 0,
-               "u2mkd_sptr_attention_forward: row strides %lld / %lld must be multiples of 4 floats and hold %d heads",
-               (long long)ld_qkv, (long long)ld_out, h);
+    U2_REQUIRE(ld_qkv >= (int64_t)h * kHd && ld_out >= (int64_t)h * kHd && ld_qkv % kRowVec<T> == 0 && ld_out % kRowVec<T> == 0,
+               "u2mkd_sptr_attention_forward: row strides %lld / %lld must be multiples of %d elements and hold %d heads",
+               (long long)ld_qkv, (long long)ld_out, kRowVec<T>, h);
+    U2_REQUIRE(sizeof(T) == 4 || sptr_aligned16({q, k, v, out}),
+               "u2mkd_sptr_attention_forward: 16-bit rows (q, k, v, out) must be 16-byte aligned");
     RelCtx rc{qgl, split_a};
     SptrLayout ly{ld_qkv, ld_out, 0, q_scale};
     size_t lds = (size_t)3 * L * 3 * kTabRow * sizeof(float);
     const float *rad = split_a > 0.f ? radial : nullptr;
     const int S = sptr_split(n, split_a);
 #define U2_SPTR_FWD(SS)                                                                                                  \
-    hipLaunchKernelGGL(sptr_attn_fwd_split_kernel<SS>, dim3((unsigned)ceil_div(n, kSptrThreads / SS), h),                \
+    hipLaunchKernelGGL((sptr_attn_fwd_split_kernel<T, SS>), dim3((unsigned)ceil_div(n, kSptrThreads / SS), h),           \
                        dim3(kSptrThreads), lds, as_stream(s), q, k, v, sort_idx, wstart, wlen, qc, rad, tq, tk, tv, L,   \
                        rc, n, h, out, lse, ly)
     if (S == 16) U2_SPTR_FWD(16);
@@ -926,11 +988,27 @@ int u2mkd_sptr_attention_forward_strided(const float *q, const float *k, const f
     else if (S == 4) U2_SPTR_FWD(4);
     else if (S == 2) U2_SPTR_FWD(2);
     else
-        hipLaunchKernelGGL(sptr_attn_fwd_kernel, dim3((unsigned)ceil_div(n, kSptrThreads), h), dim3(kSptrThreads), lds,
+        hipLaunchKernelGGL(sptr_attn_fwd_kernel<T>, dim3((unsigned)ceil_div(n, kSptrThreads), h), dim3(kSptrThreads), lds,
                            as_stream(s), q, k, v, sort_idx, wstart, wlen, qc, rad, tq, tk, tv, L, rc, n, h, out, lse, ly);
 #undef U2_SPTR_FWD
     return check_launch("u2mkd_sptr_attention_forward");
 }
+
+extern "C" {
+
+#define U2_SPTR_FWD_ARGS(T)                                                                                               \
+    const T *q, const T *k, const T *v, int64_t ld_qkv, float q_scale, const int32_t *sort_idx, const int32_t *wstart,    \
+        const int32_t *wlen, const int32_t *qc, const float *radial, const float *tq, const float *tk, const float *tv,    \
+        int32_t L, int32_t qgl, float split_a, int64_t n, int32_t h, int32_t hdim, T *out, int64_t ld_out, float *lse,     \
+        u2mkd_stream_t s
+#define U2_SPTR_FWD_CALL(T)                                                                                               \
+    sptr_forward_strided<T>((const T *)q, (const T *)k, (const T *)v, ld_qkv, q_scale, sort_idx, wstart, wlen, qc, radial, \
+                            tq, tk, tv, L, qgl, split_a, n, h, hdim, (T *)out, ld_out, lse, s)
+int u2mkd_sptr_attention_forward_strided(U2_SPTR_FWD_ARGS(float)) { return U2_SPTR_FWD_CALL(float); }
+int u2mkd_sptr_attention_forward_strided_bf16(U2_SPTR_FWD_ARGS(void)) { return U2_SPTR_FWD_CALL(bf16row); }
+int u2mkd_sptr_attention_forward_strided_f16(U2_SPTR_FWD_ARGS(void)) { return U2_SPTR_FWD_CALL(_Float16); }
+#undef U2_SPTR_FWD_ARGS
+#undef U2_SPTR_FWD_CALL
 
 int u2mkd_sptr_attention_forward(const float *q, const float *k, const float *v, const int32_t *sort_idx,
                                  const int32_t *wstart, const int32_t *wlen, const int32_t *qc, const float *radial,
@@ -958,14 +1036,16 @@ size_t u2mkd_sptr_backward_workspace_bytes(int64_t n, int32_t h, int32_t L) {
     return (size_t)2 * sptr_bwd_grid_max(n) * h * 3 * L * 3 * kHd * sizeof(float);   // one slab per wave, any split
 }
 
-int u2mkd_sptr_attention_backward_strided(const float *q, const float *k, const float *v, int64_t ld_qkv, float q_scale,
-                                          const float *out, const float *dout, int64_t ld_out,
-                                  const float *lse, const int32_t *sort_idx, const int32_t *wstart,
-                                  const int32_t *wlen, const int32_t *qc, const float *radial, const float *tq,
-                                  const float *tk, const float *tv, int32_t L, int32_t qgl, float split_a,
-                                  int32_t qc_span, int64_t n, int32_t h, int32_t hdim, float *delta /*[n,h] scratch*/,
-                                  void *workspace, size_t workspace_bytes, float *dq, float *dk, float *dv,
-                                  int64_t ld_grad, float *dtq, float *dtk, float *dtv, u2mkd_stream_t s) {
+}  // extern "C"
+
+template <typename T>
+static int sptr_backward_strided(const T *q, const T *k, const T *v, int64_t ld_qkv, float q_scale, const T *out, const T *dout,
+                                 int64_t ld_out, const float *lse, const int32_t *sort_idx, const int32_t *wstart,
+                                 const int32_t *wlen, const int32_t *qc, const float *radial, const float *tq,
+                                 const float *tk, const float *tv, int32_t L, int32_t qgl, float split_a,
+                                 int32_t qc_span, int64_t n, int32_t h, int32_t hdim, float *delta /*[n,h] scratch*/,
+                                 void *workspace, size_t workspace_bytes, T *dq, T *dk, T *dv,
+                                 int64_t ld_grad, float *dtq, float *dtk, float *dtv, u2mkd_stream_t s) {
     if (n == 0 || h == 0) return 0;
     U2_REQUIRE(q && k && v && out && dout && lse && sort_idx && wstart && wlen && qc && tq && tk && tv && delta &&
                    workspace && dq && dk && dv,
@@ -975,13 +1055,15 @@ int u2mkd_sptr_attention_backward_strided(const float *q, const float *k, const 
     if (int rc = sptr_check("u2mkd_sptr_attention_backward", n, h, hdim, L, qgl, split_a)) return rc;
     U2_REQUIRE(workspace_bytes >= u2mkd_sptr_backward_workspace_bytes(n, h, L),
                "u2mkd_sptr_attention_backward: workspace too small");
-    U2_REQUIRE(ld_qkv >= (int64_t)h * kHd && ld_out >= (int64_t)h * kHd && ld_grad >= (int64_t)h * kHd && ld_qkv % 4 == 0 &&
-                   ld_out % 4 == 0 && ld_grad % 4 == 0,
-               "u2mkd_sptr_attention_backward: row strides must be multiples of 4 floats and hold %d heads", h);
+    U2_REQUIRE(ld_qkv >= (int64_t)h * kHd && ld_out >= (int64_t)h * kHd && ld_grad >= (int64_t)h * kHd &&
+                   ld_qkv % kRowVec<T> == 0 && ld_out % kRowVec<T> == 0 && ld_grad % kRowVec<T> == 0,
+               "u2mkd_sptr_attention_backward: row strides must be multiples of %d elements and hold %d heads", kRowVec<T>, h);
+    U2_REQUIRE(sizeof(T) == 4 || sptr_aligned16({q, k, v, out, dout, dq, dk, dv}),
+               "u2mkd_sptr_attention_backward: 16-bit rows (q, k, v, out, dout, dq, dk, dv) must be 16-byte aligned");
     RelCtx rc{qgl, split_a};
     SptrLayout ly{ld_qkv, ld_out, ld_grad, q_scale};
     hipStream_t st = as_stream(s);
-    hipLaunchKernelGGL(sptr_delta_kernel, dim3((unsigned)ceil_div(n * h, 256)), dim3(256), 0, st, dout, out, sort_idx,
+    hipLaunchKernelGGL(sptr_delta_kernel<T>, dim3((unsigned)ceil_div(n * h, 256)), dim3(256), 0, st, dout, out, sort_idx,
                        n, h, delta, ld_out);
     const int S = sptr_split(n, split_a);
     const int G = sptr_bwd_grid(n, S);
@@ -999,13 +1081,13 @@ int u2mkd_sptr_attention_backward_strided(const float *q, const float *k, const 
     size_t lds_k = ((size_t)3 * tabf + (size_t)tpb * (kHistTab + 1) + tpb * kVecRow + tpb * 3) * sizeof(float);
 #define U2_SPTR_BWD(SS)                                                                                                  \
     do {                                                                                                                 \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&sptr_bwd_query_kernel<SS>),                            \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&sptr_bwd_query_kernel<T, SS>),                         \
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q);                               \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&sptr_bwd_key_kernel<SS>),                              \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&sptr_bwd_key_kernel<T, SS>),                           \
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_k);                               \
-        hipLaunchKernelGGL(sptr_bwd_query_kernel<SS>, dim3(G, h), dim3(kSptrThreads), lds_q, st, q, k, v, dout, lse,     \
+        hipLaunchKernelGGL((sptr_bwd_query_kernel<T, SS>), dim3(G, h), dim3(kSptrThreads), lds_q, st, q, k, v, dout, lse, \
                            delta, sort_idx, wstart, wlen, qc, rad, tq, tk, tv, L, rc, n, h, dq, slabs, ly);              \
-        hipLaunchKernelGGL(sptr_bwd_key_kernel<SS>, dim3(G, h), dim3(kSptrThreads), lds_k, st, q, k, v, dout, lse,       \
+        hipLaunchKernelGGL((sptr_bwd_key_kernel<T, SS>), dim3(G, h), dim3(kSptrThreads), lds_k, st, q, k, v, dout, lse,  \
                            delta, sort_idx, wstart, wlen, qc, rad, tq, tk, tv, L, rc, n, h, dk, dv, slabs, ly);          \
     } while (0)
     // S > 1: both roles in one launch (see sptr_bwd_both_kernel); S = 1 (128 tokens' strips per workgroup: 137 + 95 KB of LDS, the
@@ -1015,9 +1097,9 @@ int u2mkd_sptr_attention_backward_strided(const float *q, const float *k, const 
     const size_t lds_b = lds_q > lds_k ? lds_q : lds_k;
 #define U2_SPTR_BOTH(SS)                                                                                                 \
     do {                                                                                                                 \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&sptr_bwd_both_kernel<SS>),                             \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&sptr_bwd_both_kernel<T, SS>),                          \
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);                               \
-        hipLaunchKernelGGL(sptr_bwd_both_kernel<SS>, dim3(G, h, 2), dim3(kSptrThreads), lds_b, st, q, k, v, dout, lse,   \
+        hipLaunchKernelGGL((sptr_bwd_both_kernel<T, SS>), dim3(G, h, 2), dim3(kSptrThreads), lds_b, st, q, k, v, dout, lse, \
                            delta, sort_idx, wstart, wlen, qc, rad, tq, tk, tv, L, rc, n, h, dq, dk, dv, slabs, ly);      \
     } while (0)
     if (S > 1 && merge) {
@@ -1037,6 +1119,24 @@ int u2mkd_sptr_attention_backward_strided(const float *q, const float *k, const 
                            dtq, dtk, dtv);
     return check_launch("u2mkd_sptr_attention_backward");
 }
+
+extern "C" {
+
+#define U2_SPTR_BWD_ARGS(T)                                                                                               \
+    const T *q, const T *k, const T *v, int64_t ld_qkv, float q_scale, const T *out, const T *dout, int64_t ld_out,        \
+        const float *lse, const int32_t *sort_idx, const int32_t *wstart, const int32_t *wlen, const int32_t *qc,          \
+        const float *radial, const float *tq, const float *tk, const float *tv, int32_t L, int32_t qgl, float split_a,     \
+        int32_t qc_span, int64_t n, int32_t h, int32_t hdim, float *delta, void *workspace, size_t workspace_bytes, T *dq, \
+        T *dk, T *dv, int64_t ld_grad, float *dtq, float *dtk, float *dtv, u2mkd_stream_t s
+#define U2_SPTR_BWD_CALL(T)                                                                                               \
+    sptr_backward_strided<T>((const T *)q, (const T *)k, (const T *)v, ld_qkv, q_scale, (const T *)out, (const T *)dout,   \
+                             ld_out, lse, sort_idx, wstart, wlen, qc, radial, tq, tk, tv, L, qgl, split_a, qc_span, n, h,  \
+                             hdim, delta, workspace, workspace_bytes, (T *)dq, (T *)dk, (T *)dv, ld_grad, dtq, dtk, dtv, s)
+int u2mkd_sptr_attention_backward_strided(U2_SPTR_BWD_ARGS(float)) { return U2_SPTR_BWD_CALL(float); }
+int u2mkd_sptr_attention_backward_strided_bf16(U2_SPTR_BWD_ARGS(void)) { return U2_SPTR_BWD_CALL(bf16row); }
+int u2mkd_sptr_attention_backward_strided_f16(U2_SPTR_BWD_ARGS(void)) { return U2_SPTR_BWD_CALL(_Float16); }
+#undef U2_SPTR_BWD_ARGS
+#undef U2_SPTR_BWD_CALL
 
 /* The last launch of the backward on its own: sums the per-wave slabs u2mkd_sptr_attention_backward(_strided) left in
  * `workspace` when it was called with dtq = dtk = dtv = NULL (same n, h, L, split_a) -- on any stream ordered behind that call.

@@ -145,6 +145,8 @@ class SparseMultiheadSASphereConcat(nn.Module):
         if qkv.is_cuda and C // self.num_heads == 16 and _PACKED:
             # q = qkv[:, 0] * scale, the per-branch head slices and torch.cat([out1, out2], 1) (spherical_transformer.py
             # :192-228) all inside the two kernels, through row strides
+            # (under bf16 / fp16 autocast qkv holds stored 16-bit rows: the kernels read them as they are, compute in fp32 and
+            # hand proj 16-bit rows -- sptr.functional._ROWS16)
             x = sptr.packed_window_attention(qkv, self.scale, [cubic, sphere])
         else:
             query = qkv[:, 0] * self.scale

@@ -122,8 +122,33 @@ class WindowPlan:
 _TILES = os.environ.get('U2MKD_SPTR_TILES', '0')
 
 
-def _attention_forward(q, k, v, ld_qkv, q_scale, plan, qc, radial, tq, tk, tv, tl, qgl, split_a, n, h, d, out, ld_out, lse, st):
-    """One branch's forward on row-strided operands (q, k, v: views whose first element is the branch's first head)."""
+# U2MKD_SPTR_ROWS16 (default on; read at import like U2MKD_F16_ROWS, kept in a module attribute so a test can flip it): q, k, v
+# that arrive as STORED 16-bit rows (bf16 / fp16 autocast with its row switch on: torchsparse.nn.functional._stored16) stay in
+# that type -- the kernels widen them on load, compute in fp32 as the reference does under amp (spherical_transformer.py:221-223:
+# .float() before every sptr call) and round out / dq / dk / dv once at the store; qkv and out are saved in 16 bits.  Off: the
+# upcast formulation (one fp32 copy of the rows in, fp32 rows out), which is also what fp32 rows, the tile form (U2MKD_SPTR_TILES)
+# and the row switches at 0 take.  The forward of both formulations is the same, bit for bit; tables and their gradients are fp32.
+_ROWS16 = os.environ.get('U2MKD_SPTR_ROWS16', '1') != '0'
+
+
+def _rows16(*rows):
+    """the 16-bit dtype the attention runs ``rows`` (q, k, v or the packed qkv) in, or None: the fp32 kernels on fp32 copies"""
+    if not _ROWS16 or _TILES != '0':
+        return None
+    from ..torchsparse.nn import functional as spf
+    rt = spf._stored16(rows[0].dtype)
+    return rt if rt is not None and all(t.dtype == rt for t in rows) else None
+
+
+def _attention_forward(q, k, v, ld_qkv, q_scale, plan, qc, radial, tq, tk, tv, tl, qgl, split_a, n, h, d, out, ld_out, lse, st, rt=None):
+    """One branch's forward on row-strided operands (q, k, v: views whose first element is the branch's first head);
+    ``rt``: their 16-bit row dtype (and ``out``'s), None = fp32."""
+    if rt is not None:
+        from ..torchsparse.nn import functional as spf
+        L.call(spf._entry('u2mkd_sptr_attention_forward_strided', rt), L.ptr(q), L.ptr(k), L.ptr(v), ld_qkv, q_scale,
+               L.ptr(plan.sort_idx), L.ptr(plan.wstart), L.ptr(plan.wlen), L.ptr(qc), L.ptr(radial), L.ptr(tq), L.ptr(tk), L.ptr(tv),
+               tl, qgl, split_a, n, h, d, L.ptr(out), ld_out, L.ptr(lse), st)
+        return
     if _TILES == 'all' or (_TILES == 'sphere' and split_a > 0):
         nbytes = L.load().u2mkd_sptr_tiles_workspace_bytes(n, h)
         ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=out.device)
@@ -140,7 +165,8 @@ class WindowAttentionFunction(Function):
     @staticmethod
     def forward(ctx, q, k, v, tq, tk, tv, plan, qc, radial, qgl, split_a, qc_span=0):
         L.require_cuda(q, k, v, tq, tk, tv)
-        q, k, v = (t.contiguous().float() for t in (q, k, v))
+        rt = ctx.rows16 = _rows16(q, k, v)
+        q, k, v = (t.contiguous() if rt is not None else t.contiguous().float() for t in (q, k, v))
         tq, tk, tv = (t.contiguous().float() for t in (tq, tk, tv))
         n, h, d = q.shape
         tl = tq.shape[0]
@@ -154,7 +180,7 @@ class WindowAttentionFunction(Function):
         out = torch.empty_like(q)
         lse = torch.empty(n, h, dtype=torch.float32, device=q.device)
         _attention_forward(q, k, v, h * d, 1.0, plan, qc, radial, tq, tk, tv, tl, int(qgl), float(split_a), n, h, d, out, h * d, lse,
-                           L.stream())
+                           L.stream(), rt)
         ctx.save_for_backward(q, k, v, out, lse, tq, tk, tv, qc, radial if radial is not None else q.new_empty(0))
         ctx.plan, ctx.qgl, ctx.split_a, ctx.has_radial = plan, int(qgl), float(split_a), radial is not None
         ctx.qc_span = int(qc_span)
@@ -169,7 +195,8 @@ class WindowAttentionFunction(Function):
             return z, z, z, t, t, t, None, None, None, None, None, None
         q, k, v, out, lse, tq, tk, tv, qc, radial = ctx.saved_tensors
         plan = ctx.plan
-        dout = dout.contiguous().float()
+        rt = ctx.rows16
+        dout = dout.contiguous().to(rt or torch.float32)
         n, h, d = q.shape
         tl = tq.shape[0]
         delta = torch.empty(n, h, dtype=torch.float32, device=q.device)
@@ -177,6 +204,14 @@ class WindowAttentionFunction(Function):
         dtq, dtk, dtv = torch.empty_like(tq), torch.empty_like(tk), torch.empty_like(tv)
         nbytes = L.load().u2mkd_sptr_backward_workspace_bytes(n, h, tl)
         ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=q.device)
+        if rt is not None:
+            from ..torchsparse.nn import functional as spf
+            L.call(spf._entry('u2mkd_sptr_attention_backward_strided', rt), L.ptr(q), L.ptr(k), L.ptr(v), h * d, 1.0, L.ptr(out),
+                   L.ptr(dout), h * d, L.ptr(lse), L.ptr(plan.sort_idx), L.ptr(plan.wstart), L.ptr(plan.wlen), L.ptr(qc),
+                   L.ptr(radial) if ctx.has_radial else None, L.ptr(tq), L.ptr(tk), L.ptr(tv), tl, ctx.qgl, ctx.split_a, ctx.qc_span,
+                   n, h, d, L.ptr(delta), L.ptr(ws), nbytes, L.ptr(dq), L.ptr(dk), L.ptr(dv), h * d, L.ptr(dtq), L.ptr(dtk),
+                   L.ptr(dtv), L.stream())
+            return dq, dk, dv, dtq, dtk, dtv, None, None, None, None, None, None
         L.call('u2mkd_sptr_attention_backward', L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), L.ptr(dout), L.ptr(lse),
                L.ptr(plan.sort_idx), L.ptr(plan.wstart), L.ptr(plan.wlen), L.ptr(qc),
                L.ptr(radial) if ctx.has_radial else None, L.ptr(tq), L.ptr(tk), L.ptr(tv), tl, ctx.qgl, ctx.split_a,
@@ -197,7 +232,8 @@ class PackedAttentionFunction(Function):
     @staticmethod
     def forward(ctx, qkv, scale, branches, *tables):
         L.require_cuda(qkv, *tables)
-        qkv = qkv.contiguous().float()
+        rt = ctx.rows16 = _rows16(qkv)            # 16-bit rows stay: no fp32 copy, out and the saved tensors in that type
+        qkv = qkv.contiguous() if rt is not None else qkv.contiguous().float()
         n, three, H, d = qkv.shape
         assert three == 3 and d == 16 and len(tables) == 3 * len(branches)
         given = tables
@@ -207,7 +243,7 @@ class PackedAttentionFunction(Function):
         ctx.table_leaves = tuple(g if (g is t and g.is_leaf and g.requires_grad) else None for g, t in zip(given, tables))
         from .. import deferred
         ctx.overlap_ok = deferred.overlap_ok()
-        out = torch.empty(n, H, d, dtype=torch.float32, device=qkv.device)
+        out = torch.empty(n, H, d, dtype=rt or torch.float32, device=qkv.device)
         lses = []
         st = L.stream()
         for b, br in enumerate(branches):
@@ -221,7 +257,7 @@ class PackedAttentionFunction(Function):
                 continue
             plan = br['plan']
             _attention_forward(qkv[:, 0, h0:], qkv[:, 1, h0:], qkv[:, 2, h0:], 3 * H * d, float(scale), plan, br['qc'], br['radial'],
-                               tq, tk, tv, tq.shape[0], int(br['qgl']), float(br['split_a']), n, h, d, out[:, h0:], H * d, lse, st)
+                               tq, tk, tv, tq.shape[0], int(br['qgl']), float(br['split_a']), n, h, d, out[:, h0:], H * d, lse, st, rt)
         ctx.save_for_backward(qkv, out, *lses, *tables)
         ctx.branches, ctx.scale = branches, float(scale)
         return out.view(n, H * d)
@@ -234,7 +270,10 @@ class PackedAttentionFunction(Function):
         saved = ctx.saved_tensors
         qkv, out, lses, tables = saved[0], saved[1], saved[2:2 + nb], saved[2 + nb:]
         n, _, H, d = qkv.shape
-        dout = dout.contiguous().float()
+        from ..torchsparse.nn import functional as spf
+        rt = ctx.rows16
+        dout = spf._rows(dout, rt)
+        backward_entry = spf._entry('u2mkd_sptr_attention_backward_strided', rt)
         dqkv = torch.empty_like(qkv)            # every (q | k | v, head) column belongs to exactly one branch
         grads = []
         st = L.stream()
@@ -254,7 +293,7 @@ class PackedAttentionFunction(Function):
             ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=qkv.device)
             side = _table_side(ctx, ctx.table_leaves[3 * b:3 * b + 3], qkv.device)
             late = side is not None
-            L.call('u2mkd_sptr_attention_backward_strided', L.ptr(qkv[:, 0, h0:]), L.ptr(qkv[:, 1, h0:]), L.ptr(qkv[:, 2, h0:]),
+            L.call(backward_entry, L.ptr(qkv[:, 0, h0:]), L.ptr(qkv[:, 1, h0:]), L.ptr(qkv[:, 2, h0:]),
                    3 * H * d, ctx.scale, L.ptr(out[:, h0:]), L.ptr(dout[:, h0 * d:]), H * d, L.ptr(lses[b]),
                    L.ptr(plan.sort_idx), L.ptr(plan.wstart), L.ptr(plan.wlen), L.ptr(br['qc']), L.ptr(br['radial']),
                    L.ptr(tq), L.ptr(tk), L.ptr(tv), tl, int(br['qgl']), float(br['split_a']), int(br['span']), n, h, d,
