@@ -654,6 +654,47 @@ int u2mkd_bn_backward_apply(const void *dy, const void *x, const void *res, int3
                             const float *beta, int32_t relu, const float *sums /*[2c] over all ranks*/, void *dx, void *dres,
                             u2mkd_stream_t s);
 
+/* ---- LayerNorm over feature rows (+ the residual add in front of it) ------------
+ * replaces nn.LayerNorm (norm1 / norm2) of the SphereFormer block (spherical_transformer.py:316-348) and, in the add form,
+ * the residual sum that feeds norm2.  y = (x - mean) * rstd * gamma + beta per ROW, rstd = 1 / sqrt(var + eps), var the biased
+ * variance taken from the squared deviations of the row (held in registers; never E[x^2] - mean^2).  One launch per forward;
+ * the backward is one row pass plus a small slab sum.  Deterministic: no atomics, and the slab partition depends on n alone.
+ *   row_dtype   the dtype of the ROWS x, a, b, stream_out, y, dy, ds, dx, db [n, c]: 0 = fp32, 1 = bf16, 2 = fp16; any other
+ *               value is an error.  gamma [c], beta [c], w [n], mean [n], rstd [n], partial, dgamma [c], dbeta [c] are fp32 in
+ *               every case.  The arithmetic between a load and a store (a row's sums and statistics, the normalise and dx
+ *               expressions, the cross-lane and slab sums of dgamma / dbeta) is carried in double; every stored value is
+ *               rounded once (csrc/ln.hip, ARITHMETIC).  Rows are contiguous;
+ *               row pointers, gamma, beta and partial are 16-byte aligned (anything else is an error).
+ *   c           a multiple of 8 in 32..1024.  Any other width returns 3 ("not supported", u2mkd_last_error) and launches
+ *               nothing: the caller takes another route.  n = 0 returns 0 without a launch (and writes nothing: a caller that
+ *               needs dgamma = dbeta = 0 for an empty batch zeroes them itself).
+ *   mean, rstd  [n] out of the forward entries, together or both NULL.  NULL (a forward under no_grad: the frozen teacher)
+ *               skips their stores.
+ *   u2mkd_ln_add_forward   s = a + w_r * b in fp32 (one fma), rounded ONCE to the row type and written to stream_out -- the new
+ *               residual-stream row --, y = LN(stream_out): the statistics are taken from the ROUNDED s, so y equals
+ *               u2mkd_ln_forward applied to the stored stream_out bit for bit.  w may be NULL: s = a + b.  w is DropPath's
+ *               per-row mask / keep.  stream_out and y do not alias a or b.
+ *   u2mkd_ln_backward      serves both forms.  x is the saved input of the normalisation (x, or stream_out of the add form).
+ *               dx = rstd * (g - mean_c(g) - xhat * mean_c(g * xhat)), g = dy * gamma, xhat = (x - mean) * rstd.
+ *               ds   may be NULL.  The gradient arriving at the stream from its later consumer: dx_total = ds + dx before the
+ *                    store (one pass instead of autograd's accumulation of the two).
+ *               w, db  together or both NULL.  db = w_r * dx_total, the gradient of b; without w the gradients of a and b are
+ *                    both dx_total and the one buffer dx serves both.
+ *               partial  workspace, [u2mkd_ln_num_slabs(n, c), 2, c] floats: per slab of rows (sum dy * xhat, sum dy), accumulated
+ *                    in registers, combined across the workgroup's waves through LDS in wave order; a second kernel sums the
+ *                    slabs in a fixed order into dgamma [c] = sum_rows dy * xhat and dbeta [c] = sum_rows dy.
+ *   All launches go to the caller's stream s; nothing synchronises.                                                          */
+int64_t u2mkd_ln_num_slabs(int64_t n, int32_t c);
+int u2mkd_ln_forward(const void *x, int32_t row_dtype, int64_t n, int32_t c, const float *gamma, const float *beta, float eps,
+                     float *mean /*[n] out, may be NULL*/, float *rstd /*[n] out, may be NULL*/, void *y, u2mkd_stream_t s);
+int u2mkd_ln_add_forward(const void *a, const void *b, const float *w /*[n], may be NULL*/, int32_t row_dtype, int64_t n,
+                         int32_t c, const float *gamma, const float *beta, float eps, float *mean /*[n] out, may be NULL*/,
+                         float *rstd /*[n] out, may be NULL*/, void *stream_out, void *y, u2mkd_stream_t s);
+int u2mkd_ln_backward(const void *dy, const void *x, const void *ds /*may be NULL*/, const float *w /*[n], may be NULL*/,
+                      int32_t row_dtype, int64_t n, int32_t c, const float *mean, const float *rstd, const float *gamma,
+                      float *partial /*[slabs,2,c]*/, float *dgamma /*[c]*/, float *dbeta /*[c]*/, void *dx,
+                      void *db /*with w, else NULL*/, u2mkd_stream_t s);
+
 /* ---- SphereFormer / sptr window attention ---------------------------------------
  * replaces the extern "C" launchers of third_party/SparseTransformer/src/sptr:
  *   precompute_all_cuda_launcher            (precompute/precompute_cuda_kernel.h)

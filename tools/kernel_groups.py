@@ -10,7 +10,8 @@ GROUPS = (('miopen', 'miopen'), ('igemm', 'miopen'), ('winograd', 'miopen'), ('s
           ('devoxelize', 'pt-vox'), ('voxelize', 'pt-vox'), ('cijk', 'rocblas'), ('rocprim', 'rocprim'), ('radix', 'rocprim'),
           ('upsample', 'upsample'), ('weight_fragments', 'fragments'), ('kmap', 'kmap/hash'), ('table_', 'kmap/hash'), ('hash', 'kmap/hash'),
           ('floor_coords', 'kmap/hash'), ('downsample_keys', 'kmap/hash'), ('unpack_keys', 'kmap/hash'), ('count_kernel', 'kmap/hash'), ('ti_weights', 'kmap/hash'),
-          ('schedule', 'schedule'), ('pairs_build', 'schedule'), ('tile_', 'schedule'), ('layer_norm', 'layernorm'), ('multi_tensor', 'optimizer'),
+          ('schedule', 'schedule'), ('pairs_build', 'schedule'), ('tile_', 'schedule'), ('ln_fwd', 'layernorm'), ('ln_bwd', 'layernorm'),
+          ('layer_norm', 'layernorm'), ('multi_tensor', 'optimizer'),
           ('softmax', 'loss'), ('elementwise', 'torch-elementwise'), ('vectorized', 'torch-elementwise'), ('reduce_kernel', 'torch-reduce'),
           ('index', 'torch-index'), ('gather', 'torch-index'), ('scatter', 'torch-index'), ('cat', 'torch-cat'), ('fill', 'torch-fill'), ('copy', 'torch-copy'))
 

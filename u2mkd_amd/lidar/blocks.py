@@ -10,7 +10,7 @@ from ..torchsparse.nn import functional as spf
 from ..torchsparse.nn.utils import fapply
 
 __all__ = ['BasicConvolutionBlock', 'BasicDeconvolutionBlock', 'ResidualBlock', 'FusedSequential',
-           'PointBatchNorm1d', 'PointLinear']
+           'PointBatchNorm1d', 'PointLinear', 'RowLayerNorm']
 
 
 class PointLinear(nn.Linear):
@@ -21,6 +21,24 @@ class PointLinear(nn.Linear):
 
     def forward(self, input):
         return spf.linear(input, self.weight, self.bias)
+
+
+class RowLayerNorm(nn.LayerNorm):
+    """nn.LayerNorm over point features [N, C] on the HIP row kernels of csrc/ln.hip (the reference's SphereFormer block uses plain
+    nn.LayerNorm, spherical_transformer.py:316-348; same parameters / state-dict keys, and isinstance(m, nn.LayerNorm) holds).
+    The rows are read in their stored dtype and returned in the autocast row type (fp32 outside autocast); statistics, weight,
+    bias and their gradients stay fp32.  CPU tensors, widths the kernels do not take, elementwise_affine=False, non-contiguous
+    rows and U2MKD_ROW_LN=0 run torch's F.layer_norm exactly as nn.LayerNorm does."""
+
+    def forward(self, input, branch=None, row_scale=None):
+        if branch is not None:      # the add form (add_norm), through __call__ so that the module's hooks see it: (stream, normed)
+            return spf.add_layer_norm(input, branch, row_scale, self.normalized_shape, self.weight, self.bias, self.eps)
+        return spf.layer_norm(input, self.normalized_shape, self.weight, self.bias, self.eps)
+
+    def add_norm(self, shortcut, branch, row_scale=None):
+        """``(stream, normed)``: ``stream = shortcut + branch`` (``row_scale`` [N, 1], DropPath's mask / keep:
+        ``torch.addcmul(shortcut, branch, row_scale)``) and ``normed = LayerNorm(stream)``, in one pass forward and one backward."""
+        return self(shortcut, branch, row_scale)
 
 
 class PointBatchNorm1d(nn.BatchNorm1d):

@@ -14,7 +14,7 @@ import torch
 from torch import nn
 
 from .. import sptr
-from .blocks import PointLinear
+from .blocks import PointLinear, RowLayerNorm
 
 _PACKED = os.environ.get('U2MKD_SPTR_PACKED', '1') != '0'     # 0: slice / scale / concatenate around the contiguous kernels
 
@@ -56,6 +56,15 @@ class DropPath(nn.Module):
         keep = 1 - self.drop_prob
         mask = x.new_empty((x.shape[0],) + (1,) * (x.ndim - 1)).bernoulli_(keep)
         return torch.addcmul(shortcut, x, mask / keep)
+
+    def row_scale(self, x):
+        """``mask / keep`` [N, 1] of one use, drawn exactly as ``add_to`` draws it, or None where ``add_to`` is a plain sum: for
+        a consumer that applies it inside a pass of its own (RowLayerNorm.add_norm)"""
+        if self.drop_prob == 0. or not self.training:
+            return None
+        keep = 1 - self.drop_prob
+        mask = x.new_empty((x.shape[0],) + (1,) * (x.ndim - 1)).bernoulli_(keep)
+        return mask / keep
 
 
 class Mlp(nn.Module):
@@ -164,18 +173,19 @@ class SphereFormer(nn.Module):
         super().__init__()
         assert pe_type == 'contextual' and rel_query and rel_key and rel_value
         self.window_size = window_size
-        self.norm1 = nn.LayerNorm(dim)
+        self.norm1 = RowLayerNorm(dim)
         self.attn = SparseMultiheadSASphereConcat(dim, num_heads, window_size, window_size_sphere, quant_size,
                                                   quant_size_sphere, a)
         self.drop_path = DropPath(drop_path) if drop_path > 0. else nn.Identity()
-        self.norm2 = nn.LayerNorm(dim)
+        self.norm2 = RowLayerNorm(dim)
         self.mlp = Mlp(dim, int(dim * mlp_ratio))
 
     def forward(self, feats, xyz, batch):
         short_cut = feats
-        feats = self.attn(self.norm1(feats), xyz, batch)
-        if isinstance(self.drop_path, DropPath):
-            feats = self.drop_path.add_to(short_cut, feats)
-            return self.drop_path.add_to(feats, self.mlp(self.norm2(feats)))
-        feats = short_cut + self.drop_path(feats)
-        return feats + self.drop_path(self.mlp(self.norm2(feats)))
+        attn_out = self.attn(self.norm1(feats), xyz, batch)
+        drop = self.drop_path if isinstance(self.drop_path, DropPath) else None
+        # short_cut + drop_path(attn_out) and norm2 of that sum in one pass (the values of add_to followed by norm2)
+        feats, normed = self.norm2.add_norm(short_cut, attn_out, drop.row_scale(attn_out) if drop is not None else None)
+        if drop is not None:
+            return drop.add_to(feats, self.mlp(normed))
+        return feats + self.drop_path(self.mlp(normed))

@@ -1958,3 +1958,168 @@ def batch_norm(x: torch.Tensor, bn: torch.nn.modules.batchnorm._BatchNorm, relu:
     y = BatchNormFunction.apply(x, bn.weight, bn.bias, rm, rv, training, factor, bn.eps, relu, counter, residual)
     torch._C._increment_version(written)
     return y
+
+
+# --------------------------------------------------------------- layer norm
+# U2MKD_ROW_LN (read at import): 0 = torch's F.layer_norm everywhere, 1 = the row kernels of csrc/ln.hip for every row type;
+# unset = the per-row-type defaults below.  A row type is on by default once both measured runs of this tree are no slower than the
+# slower run of its parent in EVERY leg of that row type; the one session that measured it (NOTES N17.3) did not meet that in any
+# row type -- the KD legs did, the LidarStep legs (which run no LayerNorm) and one configs[4] run did not -- so all three are opt-in.
+_ROW_LN_DEFAULT = {torch.float32: False, torch.bfloat16: False, torch.float16: False}
+_ROW_LN_ENV = os.environ.get('U2MKD_ROW_LN')
+_ROW_LN_ON = {k: (v if _ROW_LN_ENV is None else _ROW_LN_ENV != '0') for k, v in _ROW_LN_DEFAULT.items()}
+
+
+def _ln_supported(c):
+    """the widths u2mkd_ln_* take (include/u2mkd_hip.h): a multiple of 8 in 32..1024"""
+    return c % 8 == 0 and 32 <= c <= 1024
+
+
+def _ln_rows(x, normalized_shape, weight, bias, *more):
+    """The dtype the row LayerNorm kernels run the rows ``x`` [N, C] (and ``more``, same shape) in, or None: torch's route
+    (CPU tensors, no library, an unsupported width, no affine parameters, non-contiguous rows, 16-bit rows outside autocast,
+    the row type switched off)."""
+    if not x.is_cuda or x.dim() != 2 or weight is None or bias is None or tuple(normalized_shape) != (x.shape[1],):
+        return None
+    if not _ln_supported(x.shape[1]) or weight.dtype != torch.float32 or bias.dtype != torch.float32:
+        return None
+    if not (weight.is_cuda and bias.is_cuda and weight.is_contiguous() and bias.is_contiguous()) \
+            or weight.data_ptr() % 16 or bias.data_ptr() % 16:
+        return None
+    for t in (x,) + more:
+        if t.shape != x.shape or not t.is_cuda or not t.is_contiguous() or not t.is_floating_point() or t.data_ptr() % 16:
+            return None
+    run = row_dtype()
+    if run is None:
+        # fp32 rows: autocast's layer_norm casts to fp32 too; 16-bit rows outside autocast stay torch's
+        if not torch.is_autocast_enabled('cuda') and any(t.dtype != torch.float32 for t in (x,) + more):
+            return None
+        run = torch.float32
+    elif x.dtype != run:
+        return None      # fp32 rows under 16-bit autocast: torch's autocast layer_norm normalises the fp32 values, and so does this
+    if not _ROW_LN_ON[run] or not _ln_library():
+        return None
+    return run
+
+
+_LN_LIBRARY = [None]
+
+
+def _ln_library():
+    """whether the library file is there (looked up once: the answer does not change under a running process)"""
+    if _LN_LIBRARY[0] is None:
+        _LN_LIBRARY[0] = os.path.exists(L.LIB_PATH)
+    return _LN_LIBRARY[0]
+
+
+def _ln_sums(n, c, dev):
+    """(partial workspace, dgamma, dbeta) of u2mkd_ln_backward; an empty batch has zero parameter gradients"""
+    if n == 0:
+        return None, torch.zeros(c, dtype=torch.float32, device=dev), torch.zeros(c, dtype=torch.float32, device=dev)
+    slabs = L.load().u2mkd_ln_num_slabs(n, c)
+    return (torch.empty(slabs * 2 * c, dtype=torch.float32, device=dev), torch.empty(c, dtype=torch.float32, device=dev),
+            torch.empty(c, dtype=torch.float32, device=dev))
+
+
+class LayerNormFunction(Function):
+    """nn.LayerNorm over the rows of [N, C] on the HIP kernels of csrc/ln.hip: rows in ``run`` (fp32 / bf16 / fp16), statistics,
+    parameters and parameter gradients fp32.  ``need``: a backward may follow (mean / rstd are stored only then)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps, run, need):
+        xr = x.to(run)
+        n, c = xr.shape
+        y = torch.empty_like(xr)
+        mean = torch.empty(n, dtype=torch.float32, device=x.device) if need else None
+        rstd = torch.empty(n, dtype=torch.float32, device=x.device) if need else None
+        L.call('u2mkd_ln_forward', L.ptr(xr), _row_code(run), n, c, L.ptr(gamma), L.ptr(beta), float(eps), L.ptr(mean),
+               L.ptr(rstd), L.ptr(y), L.stream())
+        if need:
+            ctx.save_for_backward(x, xr, gamma, beta, mean, rstd)      # (x: the input itself, for a double backward)
+            ctx.eps = eps
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, xr, gamma, beta, mean, rstd = ctx.saved_tensors
+        if torch.is_grad_enabled():      # create_graph: torch's own differentiable formulation
+            with torch.enable_grad():
+                y = torch.nn.functional.layer_norm(x.float(), (x.shape[1],), gamma, beta, ctx.eps).to(xr.dtype)
+                return torch.autograd.grad(y, (x, gamma, beta), dy, create_graph=True, allow_unused=True) + (None, None, None)
+        n, c = xr.shape
+        dy = dy.contiguous().to(xr.dtype)
+        partial, dgamma, dbeta = _ln_sums(n, c, xr.device)
+        dx = torch.empty_like(xr)
+        L.call('u2mkd_ln_backward', L.ptr(dy), L.ptr(xr), None, None, _row_code(xr.dtype), n, c, L.ptr(mean), L.ptr(rstd),
+               L.ptr(gamma), L.ptr(partial), L.ptr(dgamma), L.ptr(dbeta), L.ptr(dx), None, L.stream())
+        if dx.dtype != x.dtype:
+            dx = dx.to(x.dtype)
+        return dx, dgamma, dbeta, None, None, None
+
+
+class AddLayerNormFunction(Function):
+    """(stream, normed) = (a + w * b, LayerNorm(stream)) in one pass, stream rounded once to the row type and the statistics taken
+    from the rounded rows; the backward takes both gradients (d_stream from the stream's later consumer, d_normed) and makes one
+    pass: d_a = d_stream + LN'(d_normed), d_b = w * d_a."""
+
+    @staticmethod
+    def forward(ctx, a, b, w, gamma, beta, eps, need):
+        n, c = a.shape
+        wf = None if w is None else w.reshape(-1).float().contiguous()
+        s, y = torch.empty_like(a), torch.empty_like(a)
+        mean = torch.empty(n, dtype=torch.float32, device=a.device) if need else None
+        rstd = torch.empty(n, dtype=torch.float32, device=a.device) if need else None
+        L.call('u2mkd_ln_add_forward', L.ptr(a), L.ptr(b), L.ptr(wf), _row_code(a.dtype), n, c, L.ptr(gamma), L.ptr(beta),
+               float(eps), L.ptr(mean), L.ptr(rstd), L.ptr(s), L.ptr(y), L.stream())
+        ctx.set_materialize_grads(False)
+        if need:
+            ctx.save_for_backward(a, b, w, wf, s, gamma, beta, mean, rstd)
+            ctx.eps = eps
+        return s, y
+
+    @staticmethod
+    def backward(ctx, ds, dy):
+        a, b, w, wf, s, gamma, beta, mean, rstd = ctx.saved_tensors
+        n, c = s.shape
+        if torch.is_grad_enabled():      # create_graph: torch's own differentiable formulation
+            with torch.enable_grad():
+                s2 = a + b if w is None else torch.addcmul(a, b, w.reshape(n, 1).to(a.dtype))
+                y2 = torch.nn.functional.layer_norm(s2.float(), (c,), gamma, beta, ctx.eps).to(s.dtype)
+                outs, gouts = zip(*[(o, g) for o, g in ((s2, ds), (y2, dy)) if g is not None])
+                da, db, dg, dbt = torch.autograd.grad(outs, (a, b, gamma, beta), gouts, create_graph=True, allow_unused=True)
+                return da, db, None, dg, dbt, None, None
+        dy = torch.zeros_like(s) if dy is None else dy.contiguous().to(s.dtype)
+        if ds is not None:
+            ds = ds.contiguous().to(s.dtype)
+        partial, dgamma, dbeta = _ln_sums(n, c, s.device)
+        da = torch.empty_like(s)
+        db = torch.empty_like(s) if wf is not None else None
+        L.call('u2mkd_ln_backward', L.ptr(dy), L.ptr(s), L.ptr(ds), L.ptr(wf), _row_code(s.dtype), n, c, L.ptr(mean), L.ptr(rstd),
+               L.ptr(gamma), L.ptr(partial), L.ptr(dgamma), L.ptr(dbeta), L.ptr(da), L.ptr(db), L.stream())
+        return da, (da if db is None else db), None, dgamma, dbeta, None, None
+
+
+def _ln_need(*tensors):
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
+def layer_norm(x, normalized_shape, weight, bias, eps=1e-5):
+    """nn.LayerNorm's forward over rows [N, C]: ``x`` in its stored dtype, the result in the autocast row type (``row_dtype()``)
+    under autocast, fp32 otherwise -- on the row kernels where ``_ln_rows`` names a dtype, else torch's F.layer_norm."""
+    run = _ln_rows(x, normalized_shape, weight, bias)
+    if run is None:
+        return torch.nn.functional.layer_norm(x, normalized_shape, weight, bias, eps)
+    return LayerNormFunction.apply(x, weight, bias, eps, run, _ln_need(x, weight, bias))
+
+
+def add_layer_norm(shortcut, branch, row_scale, normalized_shape, weight, bias, eps=1e-5):
+    """``stream = shortcut + row_scale * branch`` (``row_scale`` [N, 1] or None: DropPath's mask / keep) and
+    ``normed = layer_norm(stream)``, as ONE pass where both inputs already are rows of the kernels' dtype; else the sum by
+    torch (``shortcut + branch`` / ``torch.addcmul``) followed by ``layer_norm``."""
+    run = _ln_rows(shortcut, normalized_shape, weight, bias, branch)
+    if run is None or shortcut.dtype != run or branch.dtype != run or \
+            (row_scale is not None and (row_scale.numel() != shortcut.shape[0] or row_scale.requires_grad)):
+        stream = shortcut + branch if row_scale is None else torch.addcmul(shortcut, branch, row_scale)
+        return stream, layer_norm(stream, normalized_shape, weight, bias, eps)
+    return AddLayerNormFunction.apply(shortcut, branch, row_scale, weight, bias, eps,
+                                      _ln_need(shortcut, branch, weight, bias))
