@@ -917,6 +917,29 @@ int u2mkd_grads_unscale_check(const int64_t *jobs, int32_t n_jobs, int64_t total
                               u2mkd_stream_t s);
 int u2mkd_sgd_batch_amp(const int64_t *jobs, int32_t n_jobs, int64_t total_chunks, float lr, float momentum, float weight_decay,
                         int32_t nesterov, int32_t contract, const float *grad_scale, const float *found_inf, u2mkd_stream_t s);
+/* torch.optim.Adam / AdamW (core/builder.py:670-718) over all parameters of a group in one launch: element for element the
+ * operations of torch/optim/adam.py:_multi_tensor_adam (non-capturable), in its order, in fp32.
+ * jobs: the table above with (parameter, gradient or 0 = skip, exp_avg, elements, first chunk, exp_avg_sq) -- the check kernel
+ * reads it as it reads an SGD table.  scalars: device float [n_jobs, window, 2] = (step_size, bias_correction2_sqrt) per job,
+ * computed on the host as torch computes them.  decay = (float)(1 - lr * wd) (decoupled != 0: AdamW), w1 = (float)(1 - beta1),
+ * w2 = (float)(1 - beta2).  form: which spelling each stage takes -- bit 0 / 1 / 2 / 3: the L2 add / lerp / addcmul / addcdiv
+ * `a + s * x` as one fused multiply-add; bits 4-5: sqrt (0 correctly rounded, 1 the hardware's approximation); bits 6-7: the
+ * division by bias_correction2_sqrt; bits 8-9: m / d (0 correctly rounded, 1 times the reciprocal, 2 times the hardware's approximate reciprocal).
+ * u2mkd_adam_batch_amp: under a GradScaler.  *found_inf != 0 -> nothing is written but the count; grad_scale as for SGD.  The
+ * bias corrections depend on how many earlier steps were applied, which the device alone knows: count_in (or NULL: window 1)
+ * holds that number, the kernel takes row `*count_in - count_known` of each job's `window` rows (clamped to the table), and
+ * with count_out (the last launch of a step on this device; another slot than count_in) one thread stores
+ * *count_in + (*found_inf == 0) there.
+ * u2mkd_debug_adam_stage: one stage of the update alone over n elements (0 lerp(a, b, s), 1 a + s * (b * c), 2 sqrt(a),
+ * 3 a / s, 4 a + s * (b / c)) -- what the tests compare with the single torch._foreach_* call. */
+int u2mkd_adam_batch(const int64_t *jobs, int32_t n_jobs, int64_t total_chunks, const float *scalars, float decay, float weight_decay,
+                     int32_t decoupled, float w1, float beta2, float w2, float eps, int32_t form, u2mkd_stream_t s);
+int u2mkd_adam_batch_amp(const int64_t *jobs, int32_t n_jobs, int64_t total_chunks, const float *scalars, int32_t window, float decay,
+                         float weight_decay, int32_t decoupled, float w1, float beta2, float w2, float eps, int32_t form,
+                         const int32_t *count_in, int32_t *count_out, int32_t count_known, const float *grad_scale,
+                         const float *found_inf, u2mkd_stream_t s);
+int u2mkd_debug_adam_stage(int32_t stage, int32_t form, const float *a, const float *b, const float *c, float scalar, float *out,
+                           int64_t n, u2mkd_stream_t s);
 
 #ifdef __cplusplus
 }

@@ -45,6 +45,9 @@ SIGNATURES = {
     'u2mkd_sgd_batch': (C.c_int, [_p, _i32, _i64, _f32, _f32, _f32, _i32, _i32, _p]),
     'u2mkd_grads_unscale_check': (C.c_int, [_p, _i32, _i64, _p, _p, _p]),
     'u2mkd_sgd_batch_amp': (C.c_int, [_p, _i32, _i64, _f32, _f32, _f32, _i32, _i32, _p, _p, _p]),
+    'u2mkd_adam_batch': (C.c_int, [_p, _i32, _i64, _p, _f32, _f32, _i32, _f32, _f32, _f32, _f32, _i32, _p]),
+    'u2mkd_adam_batch_amp': (C.c_int, [_p, _i32, _i64, _p, _i32, _f32, _f32, _i32, _f32, _f32, _f32, _f32, _i32, _p, _p, _i32, _p, _p, _p]),
+    'u2mkd_debug_adam_stage': (C.c_int, [_i32, _i32, _p, _p, _p, _f32, _p, _i64, _p]),
     'u2mkd_mailbox_alloc': (_p, [_sz]),
     'u2mkd_mailbox_free': (C.c_int, [_p]),
     'u2mkd_mailbox_post': (C.c_int, [_p, C.c_uint32, _i32, _p, _i64, _p]),

@@ -13,7 +13,7 @@ from . import distributed as D
 from . import kd as KD
 from . import torchsparse as ts
 from .losses import MixLovaszCrossEntropy
-from .optim import FusedSGD, GradScaler
+from .optim import FusedAdam, FusedAdamW, FusedSGD, GradScaler
 
 __all__ = ['cosine_schedule_with_warmup', 'make_optimizer', 'LidarStep', 'KDStep', 'TeacherWatch', 'kd_batch_to_device', 'pin_kd_batch', 'fresh_batch', 'state_dict',
            'load_state_dict', 'load_weights']
@@ -46,17 +46,17 @@ def make_optimizer(params, lr=0.24, momentum=0.9, weight_decay=1.0e-4, name='sgd
             common = dict(momentum=momentum, weight_decay=weight_decay, nesterov=nesterov)
             return FusedSGD([dict(params=rest, lr=lr, **common), dict(params=blocks, lr=lr * 0.1, **common)],
                             lr=lr, **common)
-        return torch.optim.AdamW([dict(params=rest, lr=lr, weight_decay=weight_decay),
-                                  dict(params=blocks, lr=lr * transformer_lr_scale, weight_decay=weight_decay)],
-                                 lr=lr, weight_decay=weight_decay)
+        return FusedAdamW([dict(params=rest, lr=lr, weight_decay=weight_decay),
+                           dict(params=blocks, lr=lr * transformer_lr_scale, weight_decay=weight_decay)],
+                          lr=lr, weight_decay=weight_decay)
     if isinstance(params, torch.nn.Module):
         params = params.parameters()
     if name == 'sgd':
         return FusedSGD(params, lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov)
     if name == 'adam':
-        return torch.optim.Adam(params, lr=lr, weight_decay=weight_decay)
+        return FusedAdam(params, lr=lr, weight_decay=weight_decay)
     if name == 'adamw':
-        return torch.optim.AdamW(params, lr=lr, weight_decay=weight_decay)
+        return FusedAdamW(params, lr=lr, weight_decay=weight_decay)
     raise NotImplementedError(name)
 
 
