@@ -6,14 +6,24 @@
 // HBM-bound row work.  Statistics are deterministic and cancellation-safe:
 //   pass 1  each workgroup takes a slab of rows and computes, per channel, its local
 //           mean and the centred second moment M2 around that mean (the slab is re-read
-//           from L2), float4 columns x row lanes, LDS tree over the row lanes;
-//   pass 2  64 lanes per channel merge the slabs with Chan's parallel update in a fixed
-//           order (no atomics -> bitwise reproducible), write mean / invstd and update
-//           the running statistics (unbiased variance, momentum) like nn.BatchNorm1d;
+//           from L2), float4 columns x row lanes, the row lanes' sums added out of LDS;
+//   pass 2  64 lanes per channel merge the slabs' (count, mean, M2) around a pivot that lies
+//           among the data, in a fixed order (no atomics -> bitwise reproducible), write mean /
+//           invstd and update the running statistics (unbiased variance, momentum) like
+//           nn.BatchNorm1d;
 //   pass 3  y = (x - mean) * invstd * gamma + beta [, ReLU]  (float4 elementwise).
 // Backward mirrors it: slab partial sums of dy' and dy'*xhat (dy' = dy masked by the fused
 // ReLU, recomputed from x), ordered merge, then
 //   dx = gamma * invstd * (dy' - mean(dy') - xhat * mean(dy' * xhat)).
+// ARITHMETIC.  Every sum over rows -- a slab's sum and second moment, the merge of the slabs and of the ranks, the gradient
+// sums -- is carried in double and rounded once to the fp32 value that is stored (partials, mean, M2, dgamma, dbeta): the
+// stored statistics are those of the rows to one fp32 rounding, whatever the mean and however many the rows (a channel that
+// holds one value in every row has that value as its mean and M2 = 0, exactly).  The elementwise passes carry the arithmetic
+// between a load and a store -- the normalise expression, the ReLU mask taken from it, the dx expression, the running update --
+// in double and round once, as csrc/ln.hip does: in fp32 an element of dx passed six roundings and was up to 1.9 units in
+// the last place off where torch's kernels were 0.8 off.  invstd is 1 / sqrt rounded once (bn_invstd).  Mean, invstd, M2 and
+// the sums are read as the fp32 values stored.
+// tests/row_bn_f64_ref.py bounds the same sequence carried out in fp32, which this is inside of.
 #include "common.h"
 
 #include <cstdlib>
@@ -45,10 +55,44 @@ __device__ __forceinline__ BnLayout bn_layout(int c) {
 // average in the KD step, 73 launches on the student's stream)
 constexpr int kBnRegRows = 16;
 
+// a float4 column's four sums in double (ARITHMETIC above)
+struct BnAcc4 {
+    double x, y, z, w;
+};
+__device__ __forceinline__ BnAcc4 bn_acc_zero() { return BnAcc4{0.0, 0.0, 0.0, 0.0}; }
+__device__ __forceinline__ void bn_acc_add(BnAcc4 &a, const float4 &v) {
+    a.x += (double)v.x; a.y += (double)v.y; a.z += (double)v.z; a.w += (double)v.w;
+}
+__device__ __forceinline__ void bn_acc_add(BnAcc4 &a, const BnAcc4 &v) { a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w; }
+__device__ __forceinline__ void bn_acc_add_sq(BnAcc4 &a, const float4 &v, const BnAcc4 &m) {
+    const double dx = (double)v.x - m.x, dy = (double)v.y - m.y, dz = (double)v.z - m.z, dw = (double)v.w - m.w;
+    a.x += dx * dx; a.y += dy * dy; a.z += dz * dz; a.w += dw * dw;
+}
+// invstd = 1 / sqrt(v) rounded once: the fp32 estimate refined by one Newton step in double (relative error 1e-14 before the
+// rounding; every kernel that writes or uses an invstd takes it from here, so they agree bit for bit)
+__device__ __forceinline__ float bn_invstd(double v) {
+    const double r = (double)(1.f / sqrtf((float)v));
+    return (float)(r * (1.5 - 0.5 * v * r * r));
+}
+// running' = (1 - momentum) running + momentum s, from the stored (rounded) mean and M2, one rounding
+__device__ __forceinline__ void bn_running_update(float *rm, float *rv, float momentum, float mean, double unbiased) {
+    const double mo = (double)momentum;
+    *rm = (float)((1.0 - mo) * (double)*rm + mo * (double)mean);
+    *rv = (float)((1.0 - mo) * (double)*rv + mo * unbiased);
+}
+// the normalise expression: xhat = (x - mean) invstd and pre = xhat gamma + beta + res (res 0 without a residual)
+__device__ __forceinline__ double bn_xhat(float v, float m, float is) { return ((double)v - (double)m) * (double)is; }
+__device__ __forceinline__ double bn_pre(double h, float g, float b, float rv) { return h * (double)g + (double)b + (double)rv; }
+__device__ __forceinline__ float bn_out(float v, float m, float is, float g, float b, float rv, int relu) {
+    const double o = bn_pre(bn_xhat(v, m, is), g, b, rv);
+    return (float)(relu ? fmax(o, 0.0) : o);
+}
+__device__ __forceinline__ float4 bn_acc_round(const BnAcc4 &a) { return make_float4((float)a.x, (float)a.y, (float)a.z, (float)a.w); }
+
 template <typename T>
 __global__ void __launch_bounds__(kBnThreads)
 bn_stats_partial_reg_kernel(const T *__restrict__ x, int64_t n, int c, float *__restrict__ partial) {
-    extern __shared__ __attribute__((aligned(16))) float4 red[];   // [rl][c4]
+    extern __shared__ __attribute__((aligned(16))) BnAcc4 red[];   // [rl][c4]
     const int c4 = c >> 2, rl = kBnThreads / c4;
     const int64_t r0 = (int64_t)blockIdx.x * kBnSlabRows;
     const int rows = (int)min((int64_t)kBnSlabRows, n - r0);
@@ -60,47 +104,44 @@ bn_stats_partial_reg_kernel(const T *__restrict__ x, int64_t n, int c, float *__
         const int rr = ry + u * rl;
         vals[u] = (live && rr < rows) ? ld4(x, (r0 + rr) * c4 + j) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    BnAcc4 s = bn_acc_zero();
 #pragma unroll
-    for (int u = 0; u < kBnRegRows; ++u) { s.x += vals[u].x; s.y += vals[u].y; s.z += vals[u].z; s.w += vals[u].w; }
+    for (int u = 0; u < kBnRegRows; ++u)
+        if (u * rl < rows) bn_acc_add(s, vals[u]);       // (the same for the whole workgroup; a row past the slab adds an exact zero)
     if (live) red[ry * c4 + j] = s;
     __syncthreads();
-    float4 mean = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (live) {
-        for (int g = 0; g < rl; ++g) {
-            float4 v = red[g * c4 + j];
-            mean.x += v.x; mean.y += v.y; mean.z += v.z; mean.w += v.w;
-        }
-        float inv = 1.f / (float)rows;
+    // lane 0 of each column adds the row lanes' sums and hands the mean round (every lane adding all of them for itself
+    // read rl x 256 entries out of LDS per workgroup)
+    BnAcc4 mean = bn_acc_zero();
+    if (live && ry == 0) {
+        for (int g = 0; g < rl; ++g) bn_acc_add(mean, red[g * c4 + j]);
+        const double inv = 1.0 / (double)rows;
         mean.x *= inv; mean.y *= inv; mean.z *= inv; mean.w *= inv;
     }
     __syncthreads();
-    float4 m2 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (live && ry == 0) red[j] = mean;
+    __syncthreads();
+    if (live) mean = red[j];
+    __syncthreads();
+    BnAcc4 m2 = bn_acc_zero();
 #pragma unroll
-    for (int u = 0; u < kBnRegRows; ++u) {
-        if (live && ry + u * rl < rows) {
-            float dx = vals[u].x - mean.x, dy = vals[u].y - mean.y, dz = vals[u].z - mean.z, dw = vals[u].w - mean.w;
-            m2.x += dx * dx; m2.y += dy * dy; m2.z += dz * dz; m2.w += dw * dw;
-        }
-    }
+    for (int u = 0; u < kBnRegRows; ++u)
+        if (live && ry + u * rl < rows) bn_acc_add_sq(m2, vals[u], mean);
     if (live) red[ry * c4 + j] = m2;
     __syncthreads();
     if (live && ry == 0) {
-        float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int g = 0; g < rl; ++g) {
-            float4 v = red[g * c4 + j];
-            t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w;
-        }
+        BnAcc4 t = bn_acc_zero();
+        for (int g = 0; g < rl; ++g) bn_acc_add(t, red[g * c4 + j]);
         float *p = partial + (size_t)blockIdx.x * 2 * c;
-        *reinterpret_cast<float4 *>(p + 4 * j) = mean;
-        *reinterpret_cast<float4 *>(p + c + 4 * j) = t;
+        *reinterpret_cast<float4 *>(p + 4 * j) = bn_acc_round(mean);
+        *reinterpret_cast<float4 *>(p + c + 4 * j) = bn_acc_round(t);
     }
 }
 
 template <typename T>
 __global__ void __launch_bounds__(kBnThreads)
 bn_stats_partial_kernel(const T *__restrict__ x, int64_t n, int c, float *__restrict__ partial) {
-    extern __shared__ __attribute__((aligned(16))) float4 red[];   // [rl][c4] (c4 <= 256)
+    extern __shared__ __attribute__((aligned(16))) BnAcc4 red[];   // [rl][c4] (c4 <= 256)
     const int c4 = c >> 2;
     const int nloop = (c4 + kBnThreads - 1) / kBnThreads;           // > 1 only for C > 1024
     const int64_t r0 = (int64_t)blockIdx.x * kBnSlabRows;
@@ -110,7 +151,7 @@ bn_stats_partial_kernel(const T *__restrict__ x, int64_t n, int c, float *__rest
         const int j = c4 >= kBnThreads ? it * kBnThreads + threadIdx.x : threadIdx.x % c4;
         const int ry = c4 >= kBnThreads ? 0 : threadIdx.x / c4;
         const bool live = j < c4 && ry < rl;
-        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+        BnAcc4 s = bn_acc_zero();
         if (live)
             for (int rr0 = ry; rr0 < rows; rr0 += 8 * rl) {       // (eight rows' loads in flight per trip, summed in row order)
                 float4 vv[8];
@@ -118,21 +159,22 @@ bn_stats_partial_kernel(const T *__restrict__ x, int64_t n, int c, float *__rest
                 for (int u = 0; u < 8; ++u)
                     vv[u] = rr0 + u * rl < rows ? ld4(x, (r0 + rr0 + u * rl) * c4 + j) : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-                for (int u = 0; u < 8; ++u) { s.x += vv[u].x; s.y += vv[u].y; s.z += vv[u].z; s.w += vv[u].w; }
+                for (int u = 0; u < 8; ++u) bn_acc_add(s, vv[u]);
             }
         if (live) red[ry * c4 + (j % c4)] = s;
         __syncthreads();
-        float4 mean = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (live) {
-            for (int g = 0; g < rl; ++g) {
-                float4 v = red[g * c4 + (j % c4)];
-                mean.x += v.x; mean.y += v.y; mean.z += v.z; mean.w += v.w;
-            }
-            float inv = 1.f / (float)rows;
+        BnAcc4 mean = bn_acc_zero();
+        if (live && ry == 0) {
+            for (int g = 0; g < rl; ++g) bn_acc_add(mean, red[g * c4 + (j % c4)]);
+            const double inv = 1.0 / (double)rows;
             mean.x *= inv; mean.y *= inv; mean.z *= inv; mean.w *= inv;
         }
         __syncthreads();
-        float4 m2 = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (live && ry == 0) red[j % c4] = mean;
+        __syncthreads();
+        if (live) mean = red[j % c4];
+        __syncthreads();
+        BnAcc4 m2 = bn_acc_zero();
         if (live)
             for (int rr0 = ry; rr0 < rows; rr0 += 8 * rl) {
                 float4 vv[8];
@@ -142,30 +184,28 @@ bn_stats_partial_kernel(const T *__restrict__ x, int64_t n, int c, float *__rest
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {
                     if (rr0 + u * rl >= rows) break;
-                    float dx = vv[u].x - mean.x, dy = vv[u].y - mean.y, dz = vv[u].z - mean.z, dw = vv[u].w - mean.w;
-                    m2.x += dx * dx; m2.y += dy * dy; m2.z += dz * dz; m2.w += dw * dw;
+                    bn_acc_add_sq(m2, vv[u], mean);
                 }
             }
         if (live) red[ry * c4 + (j % c4)] = m2;
         __syncthreads();
         if (live && ry == 0) {
-            float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-            for (int g = 0; g < rl; ++g) {
-                float4 v = red[g * c4 + (j % c4)];
-                t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w;
-            }
+            BnAcc4 t = bn_acc_zero();
+            for (int g = 0; g < rl; ++g) bn_acc_add(t, red[g * c4 + (j % c4)]);
             float *p = partial + (size_t)blockIdx.x * 2 * c;
-            *reinterpret_cast<float4 *>(p + 4 * j) = mean;
-            *reinterpret_cast<float4 *>(p + c + 4 * j) = t;
+            *reinterpret_cast<float4 *>(p + 4 * j) = bn_acc_round(mean);
+            *reinterpret_cast<float4 *>(p + c + 4 * j) = bn_acc_round(t);
         }
         __syncthreads();
     }
 }
 
-// 4 channels x 64 slab lanes per block: lane g merges slabs g, g+64, ... with Chan's update
-// (the loads of a lane's slabs are independent of the update chain and issued four at a time --
-// with 16 lanes the 40 dependent round trips to L2 made this tiny kernel cost 10 us), the 64
-// partial (n, mean, M2) triples are then merged in lane order through LDS (fixed order).
+// 4 channels x 64 slab lanes per block: lane g takes slabs g, g+64, ... (the loads of a lane's slabs are independent and
+// issued four at a time -- with 16 lanes the 40 dependent round trips to L2 made this tiny kernel cost 10 us) and sums, in
+// double, the slabs' counts, their means' weighted distances from a pivot K (slab 0's mean, which lies among the data:
+// nothing large is subtracted) and their second moments around K; the 64 lanes' sums are added by a fixed binary tree
+// through LDS, and mean = K + S / n, M2 = Q - S^2 / n.  No division on the way (Chan's update, two fp32 divisions per
+// slab and per tree level, was what this kernel spent its time on), fixed order, no atomics: bitwise reproducible.
 constexpr int kBnFinLanes = 64, kBnFinCh = 4;
 
 __global__ void __launch_bounds__(256)
@@ -175,10 +215,11 @@ bn_stats_finalize_kernel(const float *__restrict__ partial, int nslab, int64_t n
                          int64_t *__restrict__ num_batches_tracked = nullptr, int slab_rows = kBnSlabRows) {
     // nn.BatchNorm's step counter (a separate one-element add_ launch per layer otherwise)
     if (num_batches_tracked && blockIdx.x == 0 && threadIdx.x == 0) *num_batches_tracked += 1;
-    __shared__ float s_n[kBnFinLanes][kBnFinCh], s_m[kBnFinLanes][kBnFinCh], s_q[kBnFinLanes][kBnFinCh];
+    __shared__ double s_s[kBnFinLanes][kBnFinCh], s_q[kBnFinLanes][kBnFinCh];
     const int cl = threadIdx.x & (kBnFinCh - 1), g = threadIdx.x / kBnFinCh;
     const int ch = blockIdx.x * kBnFinCh + cl;
-    float na = 0.f, mean = 0.f, m2 = 0.f;
+    const double pivot = ch < c ? (double)partial[ch] : 0.0;
+    double ss = 0.0, qq = 0.0;
     if (ch < c) {
         for (int b0 = g; b0 < nslab; b0 += 4 * kBnFinLanes) {
             float mb[4], qb[4], nb[4];
@@ -192,35 +233,27 @@ bn_stats_finalize_kernel(const float *__restrict__ partial, int nslab, int64_t n
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 if (nb[u] == 0.f) continue;
-                float tot = na + nb[u];
-                float delta = mb[u] - mean;
-                mean += delta * (nb[u] / tot);
-                m2 += qb[u] + delta * delta * (na * nb[u] / tot);
-                na = tot;
+                const double w = (double)nb[u], d = (double)mb[u] - pivot;
+                ss += w * d;
+                qq += (double)qb[u] + w * d * d;
             }
         }
     }
-    s_n[g][cl] = na; s_m[g][cl] = mean; s_q[g][cl] = m2;
+    s_s[g][cl] = ss; s_q[g][cl] = qq;
     __syncthreads();
-    // fixed binary tree over the 64 lanes (a serial merge of 64 triples by one lane, two divisions
-    // each, made this kernel slower than the statistics pass it finishes)
     for (int stride = kBnFinLanes / 2; stride >= 1; stride >>= 1) {
         if (g < stride) {
-            float nb = s_n[g + stride][cl];
-            if (nb != 0.f) {
-                float na2 = s_n[g][cl], ma = s_m[g][cl];
-                float tot = na2 + nb;
-                float delta = s_m[g + stride][cl] - ma;
-                s_m[g][cl] = ma + delta * (nb / tot);
-                s_q[g][cl] = s_q[g][cl] + s_q[g + stride][cl] + delta * delta * (na2 * nb / tot);
-                s_n[g][cl] = tot;
-            }
+            s_s[g][cl] += s_s[g + stride][cl];
+            s_q[g][cl] += s_q[g + stride][cl];
         }
         __syncthreads();
     }
     if (g != 0 || ch >= c) return;
-    mean = s_m[0][cl];
-    m2 = s_q[0][cl];
+    const double shift = s_s[0][cl] / (double)n;
+    const double m2d = s_q[0][cl] - s_s[0][cl] * shift;
+    // from here on in fp32, from the ROUNDED mean and M2: what u2mkd_bn_merge_stats computes from one rank's stats row
+    const float mean = (float)(pivot + shift);
+    const float m2 = m2d > 0.0 ? (float)m2d : 0.f;
     float var = m2 / (float)n;
     mean_out[ch] = mean;
     if (m2_out) {   // local statistics only (cross-rank merge follows): stats row = mean[c], M2[c], count
@@ -228,11 +261,10 @@ bn_stats_finalize_kernel(const float *__restrict__ partial, int nslab, int64_t n
         if (ch == 0) m2_out[c] = (float)n;
         return;
     }
-    invstd_out[ch] = 1.f / sqrtf(var + eps);
+    invstd_out[ch] = bn_invstd((double)m2 / (double)n + (double)eps);
     if (running_mean) {
-        float unbiased = n > 1 ? m2 / (float)(n - 1) : var;
-        running_mean[ch] = (1.f - momentum) * running_mean[ch] + momentum * mean;
-        running_var[ch] = (1.f - momentum) * running_var[ch] + momentum * unbiased;
+        const double unbiased = n > 1 ? (double)m2 / (double)(n - 1) : (double)var;
+        bn_running_update(running_mean + ch, running_var + ch, momentum, mean, unbiased);
     }
 }
 
@@ -251,17 +283,9 @@ __global__ void bn_apply_kernel(const T *__restrict__ x, int64_t total4, int c4,
     float4 is = *reinterpret_cast<const float4 *>(invstd + j);
     float4 g = gamma ? *reinterpret_cast<const float4 *>(gamma + j) : make_float4(1.f, 1.f, 1.f, 1.f);
     float4 b = beta ? *reinterpret_cast<const float4 *>(beta + j) : make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 o;
-    o.x = (v.x - m.x) * is.x * g.x + b.x;
-    o.y = (v.y - m.y) * is.y * g.y + b.y;
-    o.z = (v.z - m.z) * is.z * g.z + b.z;
-    o.w = (v.w - m.w) * is.w * g.w + b.w;
-    if (res) {
-        const float4 rv = ld4(res, t);
-        o.x += rv.x; o.y += rv.y; o.z += rv.z; o.w += rv.w;
-    }
-    if (relu) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
-    st4(y, t, o);
+    const float4 rv = res ? ld4(res, t) : make_float4(0.f, 0.f, 0.f, 0.f);
+    st4(y, t, make_float4(bn_out(v.x, m.x, is.x, g.x, b.x, rv.x, relu), bn_out(v.y, m.y, is.y, g.y, b.y, rv.y, relu),
+                          bn_out(v.z, m.z, is.z, g.z, b.z, rv.z, relu), bn_out(v.w, m.w, is.w, g.w, b.w, rv.w, relu)));
 }
 
 // eval mode: y = (x - running_mean) / sqrt(running_var + eps) * gamma + beta [, relu] in ONE launch (the separate
@@ -272,27 +296,20 @@ __global__ void bn_apply_eval_kernel(const T *__restrict__ x, int64_t total4, in
                                      const float *__restrict__ beta, int relu, float *__restrict__ invstd_out,
                                      T *__restrict__ y, const T *__restrict__ res = nullptr) {
     if (blockIdx.x == 0 && invstd_out)
-        for (int ch = threadIdx.x; ch < 4 * c4; ch += blockDim.x) invstd_out[ch] = 1.f / sqrtf(var[ch] + eps);
+        for (int ch = threadIdx.x; ch < 4 * c4; ch += blockDim.x) invstd_out[ch] = bn_invstd((double)var[ch] + (double)eps);
     int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= total4) return;
     int j = (int)(t % c4) * 4;
     float4 v = ld4(x, t);
     float4 m = *reinterpret_cast<const float4 *>(mean + j);
     float4 vr = *reinterpret_cast<const float4 *>(var + j);
-    float4 is = make_float4(1.f / sqrtf(vr.x + eps), 1.f / sqrtf(vr.y + eps), 1.f / sqrtf(vr.z + eps), 1.f / sqrtf(vr.w + eps));
+    float4 is = make_float4(bn_invstd((double)vr.x + (double)eps), bn_invstd((double)vr.y + (double)eps), bn_invstd((double)vr.z + (double)eps),
+                            bn_invstd((double)vr.w + (double)eps));
     float4 g = gamma ? *reinterpret_cast<const float4 *>(gamma + j) : make_float4(1.f, 1.f, 1.f, 1.f);
     float4 b = beta ? *reinterpret_cast<const float4 *>(beta + j) : make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 o;
-    o.x = (v.x - m.x) * is.x * g.x + b.x;
-    o.y = (v.y - m.y) * is.y * g.y + b.y;
-    o.z = (v.z - m.z) * is.z * g.z + b.z;
-    o.w = (v.w - m.w) * is.w * g.w + b.w;
-    if (res) {
-        const float4 rv = ld4(res, t);
-        o.x += rv.x; o.y += rv.y; o.z += rv.z; o.w += rv.w;
-    }
-    if (relu) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
-    st4(y, t, o);
+    const float4 rv = res ? ld4(res, t) : make_float4(0.f, 0.f, 0.f, 0.f);
+    st4(y, t, make_float4(bn_out(v.x, m.x, is.x, g.x, b.x, rv.x, relu), bn_out(v.y, m.y, is.y, g.y, b.y, rv.y, relu),
+                          bn_out(v.z, m.z, is.z, g.z, b.z, rv.z, relu), bn_out(v.w, m.w, is.w, g.w, b.w, rv.w, relu)));
 }
 
 // partial: [nslab][2][C] (sum dy', sum dy' * xhat)
@@ -302,7 +319,7 @@ bn_bwd_partial_kernel(const T *__restrict__ dy, const T *__restrict__ x, int64_t
                       const float *__restrict__ mean, const float *__restrict__ invstd,
                       const float *__restrict__ gamma, const float *__restrict__ beta, int relu,
                       float *__restrict__ partial, const T *__restrict__ res = nullptr) {
-    extern __shared__ __attribute__((aligned(16))) float4 red[];   // [2][rl][c4]
+    extern __shared__ __attribute__((aligned(16))) BnAcc4 red[];   // [2][rl][c4]
     const int c4 = c >> 2;
     const int nloop = (c4 + kBnThreads - 1) / kBnThreads;
     const int64_t r0 = (int64_t)blockIdx.x * kBnSlabRows;
@@ -314,7 +331,7 @@ bn_bwd_partial_kernel(const T *__restrict__ dy, const T *__restrict__ x, int64_t
         const bool live = j < c4 && ry < rl;
         const int cw = c4 >= kBnThreads ? kBnThreads : c4;
         const int jl = c4 >= kBnThreads ? threadIdx.x : j;
-        float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1;
+        BnAcc4 s1 = bn_acc_zero(), s2 = s1;
         if (live) {
             float4 m = *reinterpret_cast<const float4 *>(mean + 4 * j);
             float4 is = *reinterpret_cast<const float4 *>(invstd + 4 * j);
@@ -336,15 +353,16 @@ bn_bwd_partial_kernel(const T *__restrict__ dy, const T *__restrict__ x, int64_t
                     if (rr0 + u * rl >= rows) break;
                     const float4 v = vv[u], rv = rr4[u];
                     float4 d = dd[u];
-                    float hx = (v.x - m.x) * is.x, hy = (v.y - m.y) * is.y, hz = (v.z - m.z) * is.z, hw = (v.w - m.w) * is.w;
+                    const double hx = bn_xhat(v.x, m.x, is.x), hy = bn_xhat(v.y, m.y, is.y), hz = bn_xhat(v.z, m.z, is.z),
+                                 hw = bn_xhat(v.w, m.w, is.w);
                     if (relu) {
-                        if (hx * g.x + b.x + rv.x <= 0.f) d.x = 0.f;
-                        if (hy * g.y + b.y + rv.y <= 0.f) d.y = 0.f;
-                        if (hz * g.z + b.z + rv.z <= 0.f) d.z = 0.f;
-                        if (hw * g.w + b.w + rv.w <= 0.f) d.w = 0.f;
+                        if (bn_pre(hx, g.x, b.x, rv.x) <= 0.0) d.x = 0.f;
+                        if (bn_pre(hy, g.y, b.y, rv.y) <= 0.0) d.y = 0.f;
+                        if (bn_pre(hz, g.z, b.z, rv.z) <= 0.0) d.z = 0.f;
+                        if (bn_pre(hw, g.w, b.w, rv.w) <= 0.0) d.w = 0.f;
                     }
-                    s1.x += d.x; s1.y += d.y; s1.z += d.z; s1.w += d.w;
-                    s2.x += d.x * hx; s2.y += d.y * hy; s2.z += d.z * hz; s2.w += d.w * hw;
+                    bn_acc_add(s1, d);
+                    s2.x += (double)d.x * hx; s2.y += (double)d.y * hy; s2.z += (double)d.z * hz; s2.w += (double)d.w * hw;
                 }
             }
             red[ry * cw + jl] = s1;
@@ -352,15 +370,14 @@ bn_bwd_partial_kernel(const T *__restrict__ dy, const T *__restrict__ x, int64_t
         }
         __syncthreads();
         if (live && ry == 0) {
-            float4 t1 = make_float4(0.f, 0.f, 0.f, 0.f), t2 = t1;
+            BnAcc4 t1 = bn_acc_zero(), t2 = t1;
             for (int gq = 0; gq < rl; ++gq) {
-                float4 a = red[gq * cw + jl], bq = red[(rl + gq) * cw + jl];
-                t1.x += a.x; t1.y += a.y; t1.z += a.z; t1.w += a.w;
-                t2.x += bq.x; t2.y += bq.y; t2.z += bq.z; t2.w += bq.w;
+                bn_acc_add(t1, red[gq * cw + jl]);
+                bn_acc_add(t2, red[(rl + gq) * cw + jl]);
             }
             float *p = partial + (size_t)blockIdx.x * 2 * c;
-            *reinterpret_cast<float4 *>(p + 4 * j) = t1;
-            *reinterpret_cast<float4 *>(p + c + 4 * j) = t2;
+            *reinterpret_cast<float4 *>(p + 4 * j) = bn_acc_round(t1);
+            *reinterpret_cast<float4 *>(p + c + 4 * j) = bn_acc_round(t2);
         }
         __syncthreads();
     }
@@ -369,10 +386,10 @@ bn_bwd_partial_kernel(const T *__restrict__ dy, const T *__restrict__ x, int64_t
 __global__ void __launch_bounds__(256)
 bn_bwd_finalize_kernel(const float *__restrict__ partial, int nslab, int c, float *__restrict__ dbeta,
                        float *__restrict__ dgamma, float *__restrict__ keep = nullptr) {
-    __shared__ float s_1[kBnFinLanes][kBnFinCh], s_2[kBnFinLanes][kBnFinCh];
+    __shared__ double s_1[kBnFinLanes][kBnFinCh], s_2[kBnFinLanes][kBnFinCh];
     const int cl = threadIdx.x & (kBnFinCh - 1), g = threadIdx.x / kBnFinCh;
     const int ch = blockIdx.x * kBnFinCh + cl;
-    float s1 = 0.f, s2 = 0.f;
+    double s1 = 0.0, s2 = 0.0;
     if (ch < c) {
         for (int b0 = g; b0 < nslab; b0 += 4 * kBnFinLanes) {
             float p1[4], p2[4];
@@ -383,21 +400,28 @@ bn_bwd_finalize_kernel(const float *__restrict__ partial, int nslab, int c, floa
                 p2[u] = b < nslab ? partial[(size_t)b * 2 * c + c + ch] : 0.f;
             }
 #pragma unroll
-            for (int u = 0; u < 4; ++u) { s1 += p1[u]; s2 += p2[u]; }
+            for (int u = 0; u < 4; ++u) { s1 += (double)p1[u]; s2 += (double)p2[u]; }
         }
     }
     s_1[g][cl] = s1; s_2[g][cl] = s2;
     __syncthreads();
+    for (int stride = kBnFinLanes / 2; stride >= 1; stride >>= 1) {      // (fixed binary tree over the 64 lanes)
+        if (g < stride) {
+            s_1[g][cl] += s_1[g + stride][cl];
+            s_2[g][cl] += s_2[g + stride][cl];
+        }
+        __syncthreads();
+    }
     if (g != 0 || ch >= c) return;
-    for (int i = 1; i < kBnFinLanes; ++i) { s1 += s_1[i][cl]; s2 += s_2[i][cl]; }
-    dbeta[ch] = s1;
-    dgamma[ch] = s2;
-    if (keep) { keep[ch] = s1; keep[c + ch] = s2; }      // a second copy: the first one is summed over the ranks in place
+    const float f1 = (float)s_1[0][cl], f2 = (float)s_2[0][cl];
+    dbeta[ch] = f1;
+    dgamma[ch] = f2;
+    if (keep) { keep[ch] = f1; keep[c + ch] = f2; }      // a second copy: the first one is summed over the ranks in place
 }
 
 template <typename T>
 __global__ void bn_bwd_apply_kernel(const T *__restrict__ dy, const T *__restrict__ x, int64_t total4, int c4,
-                                    float inv_n_host, const float *__restrict__ total_n,
+                                    double inv_n_host, const float *__restrict__ total_n,
                                     const float *__restrict__ mean, const float *__restrict__ invstd,
                                     const float *__restrict__ gamma, const float *__restrict__ beta, int relu,
                                     const float *__restrict__ dbeta, const float *__restrict__ dgamma,
@@ -405,7 +429,7 @@ __global__ void bn_bwd_apply_kernel(const T *__restrict__ dy, const T *__restric
                                     T *__restrict__ dres = nullptr) {
     int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= total4) return;
-    const float inv_n = total_n ? 1.f / *total_n : inv_n_host;     // SyncBatchNorm: the count of all ranks
+    const double inv_n = total_n ? 1.0 / (double)*total_n : inv_n_host;     // SyncBatchNorm: the count of all ranks
     int j = (int)(t % c4) * 4;
     float4 v = ld4(x, t);
     float4 d = ld4(dy, t);
@@ -415,20 +439,20 @@ __global__ void bn_bwd_apply_kernel(const T *__restrict__ dy, const T *__restric
     float4 b = beta ? *reinterpret_cast<const float4 *>(beta + j) : make_float4(0.f, 0.f, 0.f, 0.f);
     float4 db = *reinterpret_cast<const float4 *>(dbeta + j);
     float4 dg = *reinterpret_cast<const float4 *>(dgamma + j);
-    float hx = (v.x - m.x) * is.x, hy = (v.y - m.y) * is.y, hz = (v.z - m.z) * is.z, hw = (v.w - m.w) * is.w;
+    const double hx = bn_xhat(v.x, m.x, is.x), hy = bn_xhat(v.y, m.y, is.y), hz = bn_xhat(v.z, m.z, is.z), hw = bn_xhat(v.w, m.w, is.w);
     if (relu) {
         const float4 rv = res ? ld4(res, t) : make_float4(0.f, 0.f, 0.f, 0.f);
-        if (hx * g.x + b.x + rv.x <= 0.f) d.x = 0.f;
-        if (hy * g.y + b.y + rv.y <= 0.f) d.y = 0.f;
-        if (hz * g.z + b.z + rv.z <= 0.f) d.z = 0.f;
-        if (hw * g.w + b.w + rv.w <= 0.f) d.w = 0.f;
+        if (bn_pre(hx, g.x, b.x, rv.x) <= 0.0) d.x = 0.f;
+        if (bn_pre(hy, g.y, b.y, rv.y) <= 0.0) d.y = 0.f;
+        if (bn_pre(hz, g.z, b.z, rv.z) <= 0.0) d.z = 0.f;
+        if (bn_pre(hw, g.w, b.w, rv.w) <= 0.0) d.w = 0.f;
     }
     if (dres) st4(dres, t, d);          // gradient of the residual branch = the masked dy
     float4 o;
-    o.x = g.x * is.x * (d.x - db.x * inv_n - hx * dg.x * inv_n);
-    o.y = g.y * is.y * (d.y - db.y * inv_n - hy * dg.y * inv_n);
-    o.z = g.z * is.z * (d.z - db.z * inv_n - hz * dg.z * inv_n);
-    o.w = g.w * is.w * (d.w - db.w * inv_n - hw * dg.w * inv_n);
+    o.x = (float)((double)g.x * (double)is.x * ((double)d.x - (double)db.x * inv_n - hx * ((double)dg.x * inv_n)));
+    o.y = (float)((double)g.y * (double)is.y * ((double)d.y - (double)db.y * inv_n - hy * ((double)dg.y * inv_n)));
+    o.z = (float)((double)g.z * (double)is.z * ((double)d.z - (double)db.z * inv_n - hz * ((double)dg.z * inv_n)));
+    o.w = (float)((double)g.w * (double)is.w * ((double)d.w - (double)db.w * inv_n - hw * ((double)dg.w * inv_n)));
     st4(dx, t, o);
 }
 
@@ -450,18 +474,19 @@ __global__ void bn_bwd_eval_kernel(const T *__restrict__ dy, const T *__restrict
     float4 b = beta ? *reinterpret_cast<const float4 *>(beta + j) : make_float4(0.f, 0.f, 0.f, 0.f);
     if (relu) {
         const float4 rv = res ? ld4(res, t) : make_float4(0.f, 0.f, 0.f, 0.f);
-        if ((v.x - m.x) * is.x * g.x + b.x + rv.x <= 0.f) d.x = 0.f;
-        if ((v.y - m.y) * is.y * g.y + b.y + rv.y <= 0.f) d.y = 0.f;
-        if ((v.z - m.z) * is.z * g.z + b.z + rv.z <= 0.f) d.z = 0.f;
-        if ((v.w - m.w) * is.w * g.w + b.w + rv.w <= 0.f) d.w = 0.f;
+        if (bn_pre(bn_xhat(v.x, m.x, is.x), g.x, b.x, rv.x) <= 0.0) d.x = 0.f;
+        if (bn_pre(bn_xhat(v.y, m.y, is.y), g.y, b.y, rv.y) <= 0.0) d.y = 0.f;
+        if (bn_pre(bn_xhat(v.z, m.z, is.z), g.z, b.z, rv.z) <= 0.0) d.z = 0.f;
+        if (bn_pre(bn_xhat(v.w, m.w, is.w), g.w, b.w, rv.w) <= 0.0) d.w = 0.f;
     }
     if (dres) st4(dres, t, d);
-    st4(dx, t, make_float4(d.x * g.x * is.x, d.y * g.y * is.y, d.z * g.z * is.z, d.w * g.w * is.w));
+    st4(dx, t, make_float4((float)((double)d.x * (double)g.x * (double)is.x), (float)((double)d.y * (double)g.y * (double)is.y),
+                           (float)((double)d.z * (double)g.z * (double)is.z), (float)((double)d.w * (double)g.w * (double)is.w)));
 }
 
 __global__ void bn_invstd_kernel(const float *__restrict__ var, int c, float eps, float *__restrict__ invstd) {
     int ch = blockIdx.x * blockDim.x + threadIdx.x;
-    if (ch < c) invstd[ch] = 1.f / sqrtf(var[ch] + eps);
+    if (ch < c) invstd[ch] = bn_invstd((double)var[ch] + (double)eps);
 }
 
 // SyncBatchNorm: merge the per-rank (mean, M2, count) triples (rank order, Chan's update), write
@@ -474,25 +499,26 @@ __global__ void bn_sync_merge_kernel(const float *__restrict__ gathered, int wor
     if (num_batches_tracked && ch == 0) *num_batches_tracked += 1;      // nn.BatchNorm's step counter (no launch of its own)
     if (ch >= c) return;
     const int row = 2 * c + 1;
-    float na = 0.f, mean = 0.f, m2 = 0.f;
+    // (the update in double, the merged mean and M2 rounded once: with one rank they are that rank's own, bit for bit)
+    double nad = 0.0, meand = 0.0, m2d = 0.0;
     for (int r = 0; r < world; ++r) {
-        float nb = gathered[(size_t)r * row + 2 * c];
-        if (nb == 0.f) continue;
-        float mb = gathered[(size_t)r * row + ch], qb = gathered[(size_t)r * row + c + ch];
-        float tot = na + nb;
-        float delta = mb - mean;
-        mean += delta * (nb / tot);
-        m2 += qb + delta * delta * (na * nb / tot);
-        na = tot;
+        const double nb = (double)gathered[(size_t)r * row + 2 * c];
+        if (nb == 0.0) continue;
+        const double mb = (double)gathered[(size_t)r * row + ch], qb = (double)gathered[(size_t)r * row + c + ch];
+        const double tot = nad + nb;
+        const double delta = mb - meand;
+        meand += delta * (nb / tot);
+        m2d += qb + delta * delta * (nad * nb / tot);
+        nad = tot;
     }
+    const float na = (float)nad, mean = (float)meand, m2 = (float)m2d;
     float var = na > 0.f ? m2 / na : 0.f;
     mean_out[ch] = mean;
-    invstd_out[ch] = 1.f / sqrtf(var + eps);
+    invstd_out[ch] = bn_invstd((na > 0.f ? (double)m2 / (double)na : 0.0) + (double)eps);
     if (ch == 0) *total_out = na;
     if (running_mean) {
-        float unbiased = na > 1.f ? m2 / (na - 1.f) : var;
-        running_mean[ch] = (1.f - momentum) * running_mean[ch] + momentum * mean;
-        running_var[ch] = (1.f - momentum) * running_var[ch] + momentum * unbiased;
+        const double unbiased = na > 1.f ? (double)m2 / ((double)na - 1.0) : (double)var;
+        bn_running_update(running_mean + ch, running_var + ch, momentum, mean, unbiased);
     }
 }
 
@@ -500,7 +526,7 @@ static size_t bn_lds_bytes(int c, int arrays) {
     int c4 = c / 4;
     int rl = c4 >= kBnThreads ? 1 : kBnThreads / c4;
     int cw = c4 >= kBnThreads ? kBnThreads : c4;
-    return (size_t)arrays * rl * cw * sizeof(float4);
+    return (size_t)arrays * rl * cw * sizeof(BnAcc4);
 }
 
 // ---- launch sequences, shared by the fp32-, bf16- and fp16-row entry points ------------------------------------
@@ -594,7 +620,7 @@ static int bn_backward_impl(const T *dy, const T *x, const T *res, int64_t n, in
     int64_t total4 = n * (c / 4);
     if (training)
         hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, dim3((unsigned)ceil_div(total4, 256)), dim3(256), 0, st, dy, x, total4,
-                           c / 4, 1.f / (float)n, (const float *)nullptr, mean, invstd, gamma, beta, relu, dbeta, dgamma,
+                           c / 4, 1.0 / (double)n, (const float *)nullptr, mean, invstd, gamma, beta, relu, dbeta, dgamma,
                            dx, res, dres);
     else
         hipLaunchKernelGGL(bn_bwd_eval_kernel<T>, dim3((unsigned)ceil_div(total4, 256)), dim3(256), 0, st, dy, x, total4,
@@ -660,7 +686,7 @@ static int bn_backward_apply_impl(const T *dy, const T *x, const T *res, int64_t
     U2_REQUIRE(dy && x && total_n && mean && invstd && sums && dx, "u2mkd_bn_backward_apply: null pointer");
     int64_t total4 = n * (c / 4);
     hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, dim3((unsigned)ceil_div(total4, 256)), dim3(256), 0, as_stream(s), dy, x,
-                       total4, c / 4, 0.f, total_n, mean, invstd, gamma, beta, relu, sums, sums + c, dx, res, dres);
+                       total4, c / 4, 0.0, total_n, mean, invstd, gamma, beta, relu, sums, sums + c, dx, res, dres);
     return check_launch("u2mkd_bn_backward_apply");
 }
 
