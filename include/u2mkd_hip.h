@@ -775,6 +775,32 @@ int u2mkd_sptr_attention_backward_strided(const float *q, const float *k, const 
 int u2mkd_sptr_table_reduce(const void *workspace, int64_t n, int32_t h, int32_t L, float split_a, float *dtq, float *dtk,
                             float *dtv, u2mkd_stream_t s);
 
+/* The quantiser of a SHIFTED window plan (sptr/modules.py:42-44 with shift_win=True):
+ * qc = floor((((xyz - lo) + shift) % window) / quant) per sorted position, shift = window / 2 per axis (passed in: the
+ * fp32 product 0.5 * window), lo = the minimum of the UNSHIFTED coordinates.  u2mkd_sptr_quant_coords is this with
+ * shift = 0.  A shifted plan's keys are u2mkd_sptr_window_keys on xyz + shift with lo4 = (min of xyz, 0) and
+ * hi4 = (max of xyz + shift, max batch): sptr/utils.py:63-64.                                                         */
+int u2mkd_sptr_quant_coords_shifted(const float *xyz /*[n,3]*/, const int32_t *sort_idx /*[n]*/, int64_t n, const float *lo,
+                                    float wx, float wy, float wz, float shx, float shy, float shz, float qx, float qy,
+                                    float qz, int32_t *qc /*[n,3]*/, float *radial /*[n] or NULL*/, u2mkd_stream_t s);
+
+/* ---- table-free window attention (csrc/sptr_plain.hip; pe_type 'none' / 'sine' / 'fourier' of sptr/modules.py:53-61) ----
+ * out_i = sum_j softmax_j(q_scale q_i . k_j) v_j over the window of token i, on the plan arrays of the entries above
+ * (sort_idx, wstart, wlen) with the same row strides and q_scale; fp32 rows, head dim 16.  Rows move as 16-byte accesses: strides
+ * in multiples of 4 floats, row pointers 16-byte aligned (anything else is refused).  No tables, no quantised
+ * coordinates, no LDS, no workspace.  lse [n,h] per sorted position; the backward recomputes the scores from it, `delta`
+ * [n,h] is scratch.  dq (already multiplied by q_scale), dk, dv are each written by the lanes that own the row -- no
+ * atomics: the same bits on every run.  Lanes per (token, head): U2MKD_SPTR_SPLIT = 1 / 2 / 4 / 8 / 16 (read on every
+ * call), otherwise chosen from n.                                                                                      */
+int u2mkd_sptr_plain_forward_strided(const float *q, const float *k, const float *v, int64_t ld_qkv, float q_scale,
+                                     const int32_t *sort_idx, const int32_t *wstart, const int32_t *wlen, int64_t n,
+                                     int32_t h, int32_t hdim, float *out, int64_t ld_out, float *lse, u2mkd_stream_t s);
+int u2mkd_sptr_plain_backward_strided(const float *q, const float *k, const float *v, int64_t ld_qkv, float q_scale,
+                                      const float *out, const float *dout, int64_t ld_out, const float *lse,
+                                      const int32_t *sort_idx, const int32_t *wstart, const int32_t *wlen, int64_t n,
+                                      int32_t h, int32_t hdim, float *delta /*[n,h] scratch*/, float *dq, float *dk,
+                                      float *dv, int64_t ld_grad, u2mkd_stream_t s);
+
 /* ---- the `sptr_cuda` extension, function for function (csrc/sptr_ops.hip) ----------------------------------------
  * The ten functions third_party/SparseTransformer/src/sptr/pointops_api.cpp:9-20 exports, for a caller that keeps
  * sptr's Python layer (sptr/functional.py) and its M = sum_w L_w^2 pair arrays: u2mkd_sptr_<name> replaces

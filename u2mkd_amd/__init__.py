@@ -31,7 +31,9 @@ def install_as_sptr():
     the ``sptr_cuda`` extension (third_party/SparseTransformer/setup.py) and installing torch_scatter /
     torch_geometric / torch_cluster.  Parent packages that are not importable are registered as empty
     namespace modules; an existing ``third_party`` package is left in place and only its
-    ``SparseTransformer.sptr`` entry is overridden."""
+    ``SparseTransformer.sptr`` entry is overridden.  The library's own top-level name is served too --
+    ``from sptr import VarLengthMultiheadSA`` (SparseTransformer's README), ``sptr.modules``, ``sptr.utils``,
+    ``sptr.position_embedding``, ``sptr.functional`` -- unless another ``sptr`` is already imported."""
     import importlib
     import sys
     import types
@@ -51,8 +53,12 @@ def install_as_sptr():
         parent = mod
     sys.modules['third_party.SparseTransformer.sptr'] = drop_in
     parent.sptr = drop_in
-    for sub in ('functional',):
-        sys.modules['third_party.SparseTransformer.sptr.' + sub] = importlib.import_module('u2mkd_amd.sptr.' + sub)
+    top = sys.modules.setdefault('sptr', drop_in) is drop_in
+    for sub in ('functional', 'modules', 'utils', 'position_embedding'):
+        mod = importlib.import_module('u2mkd_amd.sptr.' + sub)
+        sys.modules['third_party.SparseTransformer.sptr.' + sub] = mod
+        if top:
+            sys.modules['sptr.' + sub] = mod
     return drop_in
 
 

@@ -186,6 +186,26 @@ __global__ void quant_coords_kernel(const float *__restrict__ xyz, const int32_t
     if (radial) radial[p] = xyz[t * 3 + 2];
 }
 
+// the same on a SHIFTED plan (sptr/modules.py:42-44, shift_win=True): floor((((xyz - min) + window / 2) % window) / quant),
+// min = the minimum of the unshifted coordinates; fp32 in torch's order (subtract, add the shift, fmod, floor-divide)
+__global__ void quant_coords_shifted_kernel(const float *__restrict__ xyz, const int32_t *__restrict__ sort_idx, int64_t n,
+                                            const float *__restrict__ lo, float wx, float wy, float wz, float shx, float shy,
+                                            float shz, float qx, float qy, float qz, int32_t *__restrict__ qc,
+                                            float *__restrict__ radial) {
+    int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    int64_t t = sort_idx[p];
+    const float w[3] = {wx, wy, wz}, sh[3] = {shx, shy, shz}, qs[3] = {qx, qy, qz};
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        float v = xyz[t * 3 + d] - lo[d] + sh[d];
+        float m = fmodf(v, w[d]);
+        if ((m != 0.f) && ((w[d] < 0.f) != (m < 0.f))) m += w[d];
+        qc[p * 3 + d] = (int32_t)div_floor(m, qs[d]);
+    }
+    if (radial) radial[p] = xyz[t * 3 + 2];
+}
+
 // s_tab: [3 tables][L][3][kTabRow]
 __device__ __forceinline__ void load_tables(float *s_tab, const float *tq, const float *tk, const float *tv, int L,
                                             int h, int hh) {
@@ -219,16 +239,7 @@ __device__ __forceinline__ void tab_sum(const float *tab, const int r[3], float 
 // online softmax, lse, delta, the histogram strips, the MFMA contraction, the slabs -- is the same fp32 code for every T,
 // and a result is rounded to nearest-even ONCE at its store (fp16: beyond +-65504 -> inf, never saturated).  A 16-bit row
 // is 32 bytes: the entries require 16-byte aligned rows, so its four ld4 / st4 are two 16-byte accesses.
-template <typename T>
-__device__ __forceinline__ void load16(const T *p, float out[kHd]) {
-    if constexpr (sizeof(T) == 2) p = static_cast<const T *>(__builtin_assume_aligned(p, 16));
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-        float4 x = ld4<T>(p, v);
-        out[4 * v] = x.x; out[4 * v + 1] = x.y; out[4 * v + 2] = x.z; out[4 * v + 3] = x.w;
-    }
-}
-
+// (load16: sptr_internal.h)
 // A product that goes straight to a 16-bit store: the value rounded to 16 bits is the fp32 PRODUCT (rounded to fp32), the number
 // the fp32 kernels store and a later cast rounds.  Left to instruction selection, fp16 gets v_fma_mixlo_f16 / _mixhi_f16, which
 // round the exact product once: the last place of ~1 stored value in 10^4 differed from the fp32 kernel's (MI355X,
@@ -241,12 +252,7 @@ __device__ __forceinline__ float product32(float x) {
     return x;
 }
 
-template <typename T>
-__device__ __forceinline__ void store16(T *p, const float x[kHd]) {
-    if constexpr (sizeof(T) == 2) p = static_cast<T *>(__builtin_assume_aligned(p, 16));
-#pragma unroll
-    for (int v = 0; v < 4; ++v) st4<T>(p, v, make_float4(x[4 * v], x[4 * v + 1], x[4 * v + 2], x[4 * v + 3]));
-}
+// (store16: sptr_internal.h)
 
 // ---- forward: out[t,h,:] = softmax_j(s) . (v_j + Tv(rel)),  lse saved per (sorted pos, head)
 template <typename T>
@@ -399,32 +405,7 @@ sptr_attn_fwd_split_kernel(const T *__restrict__ q, const T *__restrict__ k, con
     }
 }
 
-// delta[p,h] = sum_d dout[t,h,d] * out[t,h,d]
-template <typename T>
-__global__ void sptr_delta_kernel(const T *__restrict__ dout, const T *__restrict__ out,
-                                  const int32_t *__restrict__ sort_idx, int64_t n, int h, float *__restrict__ delta,
-                                  int64_t ld_out) {
-    int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n * h) return;
-    int64_t p = e / h;
-    int hh = (int)(e - p * h);
-    int64_t t = sort_idx[p];
-    float s = 0.f;
-    if constexpr (sizeof(T) == 4) {
-        const float *a = dout + t * ld_out + hh * kHd, *b = out + t * ld_out + hh * kHd;
-#pragma unroll
-        for (int d = 0; d < kHd; ++d) s += a[d] * b[d];
-    } else {
-        float a[kHd], b[kHd];
-        load16(dout + t * ld_out + hh * kHd, a);
-        load16(out + t * ld_out + hh * kHd, b);
-#pragma unroll
-        for (int d = 0; d < kHd; ++d) s += a[d] * b[d];
-    }
-    delta[e] = s;
-}
-
-
+// (sptr_delta_kernel: sptr_internal.h, shared with csrc/sptr_plain.hip)
 
 // ---- backward, histogram form (the default) ----------------------------------------------------
 // LDS float atomics run at a small fraction of the LDS rate on gfx950 (144 of them per (query, key)
@@ -925,15 +906,25 @@ int u2mkd_sptr_quant_coords(const float *xyz, const int32_t *sort_idx, int64_t n
     return check_launch("u2mkd_sptr_quant_coords");
 }
 
+int u2mkd_sptr_quant_coords_shifted(const float *xyz, const int32_t *sort_idx, int64_t n, const float *lo, float wx, float wy,
+                                    float wz, float shx, float shy, float shz, float qx, float qy, float qz, int32_t *qc,
+                                    float *radial, u2mkd_stream_t s) {
+    if (n == 0) return 0;
+    U2_REQUIRE(xyz && sort_idx && lo && qc, "u2mkd_sptr_quant_coords_shifted: null pointer");
+    U2_REQUIRE(wx > 0 && wy > 0 && wz > 0 && qx > 0 && qy > 0 && qz > 0,
+               "u2mkd_sptr_quant_coords_shifted: window and quantisation sizes must be positive");
+    hipLaunchKernelGGL(quant_coords_shifted_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, as_stream(s), xyz,
+                       sort_idx, n, lo, wx, wy, wz, shx, shy, shz, qx, qy, qz, qc, radial);
+    return check_launch("u2mkd_sptr_quant_coords_shifted");
+}
+
 // Lanes per (token, head).  The window length is only known on the device; what the host knows is the token count
 // and the branch: the cubic windows hold a few tokens at every stage, the spherical windows grow as the token count
 // shrinks (coarser stages, wider cones).  U2MKD_SPTR_SPLIT = 1 / 2 / 4 / 8 / 16 overrides, on either branch (A/B runs,
 // tests/test_gpu_sptr_splits.py); it is read on every call, so it must not change between a backward and the
 // u2mkd_sptr_table_reduce that sums its slabs.
 static int sptr_split(int64_t n, float split_a) {
-    const char *e = getenv("U2MKD_SPTR_SPLIT");
-    const int forced = e ? atoi(e) : 0;
-    if (forced == 1 || forced == 2 || forced == 4 || forced == 8 || forced == 16) return forced;
+    if (const int forced = sptr_forced_split()) return forced;
     if (split_a <= 0.f) return 1;
     return n < 12000 ? 16 : n < 24000 ? 8 : n < 48000 ? 4 : 2;
 }

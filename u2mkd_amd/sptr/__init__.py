@@ -1,6 +1,7 @@
 """Drop-in for ``third_party.SparseTransformer.sptr`` on MI355X: the four names
 core/models/sphereformer/spherical_transformer.py:7 imports (``to_3d_numpy``, ``SparseTrTensor``,
-``sparse_self_attention``, ``get_indices_params``).
+``sparse_self_attention``, ``get_indices_params``) and the library's module surface (``VarLengthMultiheadSA``,
+``PositionEmbeddingCoordsSine``; submodules ``modules``, ``utils``, ``position_embedding``, ``functional``).
 
 ``get_indices_params`` returns a :class:`WindowPlan` in place of the reference's ``index_0`` (and inert
 placeholders for the other M-sized index tensors): the HIP attention never materialises the
@@ -11,10 +12,12 @@ import numbers
 
 import numpy as np
 
-from .functional import WindowPlan, get_indices_params, packed_window_attention, sparse_self_attention, window_attention
+from .functional import (WindowPlan, get_indices_params, packed_window_attention, plain_window_attention, sparse_self_attention,
+                         window_attention)
 
 __all__ = ['to_3d_numpy', 'SparseTrTensor', 'sparse_self_attention', 'get_indices_params', 'WindowPlan',
-           'window_attention', 'packed_window_attention']
+           'window_attention', 'packed_window_attention', 'plain_window_attention', 'VarLengthMultiheadSA',
+           'PositionEmbeddingCoordsSine']
 
 
 def to_3d_numpy(size):
@@ -55,3 +58,8 @@ class SparseTrTensor:
     def find_indice_params(self, key):
         """Cached index structure stored under ``key`` (None when absent or when ``key`` is None)."""
         return None if key is None else self.indice_dict.get(key)
+
+
+# (after the names above: modules.py imports them from this package, as the reference's does)
+from .position_embedding import PositionEmbeddingCoordsSine  # noqa: E402
+from .modules import VarLengthMultiheadSA  # noqa: E402

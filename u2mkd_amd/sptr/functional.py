@@ -1,5 +1,5 @@
-"""Window attention with contextual relative position tables on the HIP kernels of
-csrc/sptr.hip (rows a10-a11 of SURVEY.md §8a)."""
+"""Window attention on the HIP kernels of csrc/sptr.hip (contextual relative position tables) and csrc/sptr_plain.hip
+(table-free), on plain or shifted window plans (rows a10-a11 of SURVEY.md §8a)."""
 from __future__ import annotations
 
 import numpy as np
@@ -10,7 +10,7 @@ from torch.autograd import Function
 
 from .. import _lib as L
 
-__all__ = ['WindowPlan', 'get_indices_params', 'sparse_self_attention', 'window_attention']
+__all__ = ['WindowPlan', 'get_indices_params', 'sparse_self_attention', 'window_attention', 'plain_window_attention']
 
 
 class _Inert:
@@ -25,9 +25,16 @@ class _Inert:
 
 class WindowPlan:
     """Tokens sorted by window: ``sort_idx`` (token id at sorted position), and per sorted
-    position the first position / length of its window.  Built with no host sync."""
+    position the first position / length of its window.  Built with no host sync.
 
-    def __init__(self, xyz: torch.Tensor, batch: torch.Tensor, window_size):
+    ``shift_win``: the windows of sptr/utils.py:63-64 -- the grid moved by half a window: the cluster key of
+    ``voxel_grid(xyz + 1/2 * window_size, batch, window_size, start=xyz.min(0)[0])``, i.e. start = the minimum of the UNSHIFTED
+    coordinates (0 on the batch axis), end = the maximum of the shifted ones, fp32 in torch's order.  ``lo`` stays the unshifted
+    minimum (what the quantiser subtracts)."""
+
+    shift_win = False
+
+    def __init__(self, xyz: torch.Tensor, batch: torch.Tensor, window_size, shift_win: bool = False):
         L.require_cuda(xyz, batch)
         xyz = xyz.contiguous().float()
         n = xyz.shape[0]
@@ -38,7 +45,15 @@ class WindowPlan:
         lo4 = p4.amin(0).contiguous()
         hi4 = p4.amax(0).contiguous()
         keys = torch.empty(n, dtype=torch.int64, device=dev)
-        L.call('u2mkd_sptr_window_keys', L.ptr(xyz), L.ptr(b32), n, L.ptr(lo4), L.ptr(hi4), w[0], w[1], w[2],
+        self.shift_win = bool(shift_win)
+        if len(w) == 1:
+            w = w * 3
+        pos, lo_k, hi_k = xyz, lo4, hi4
+        if self.shift_win:
+            pos = xyz + 0.5 * torch.tensor(w, dtype=torch.float32, device=dev)
+            lo_k = torch.cat([lo4[:3], lo4.new_zeros(1)])
+            hi_k = torch.cat([pos.amax(0), hi4[3:]]) if n else hi4
+        L.call('u2mkd_sptr_window_keys', L.ptr(pos), L.ptr(b32), n, L.ptr(lo_k), L.ptr(hi_k), w[0], w[1], w[2],
                L.ptr(keys), L.stream())
         self._finish(n, keys, lo4, w)
 
@@ -98,8 +113,13 @@ class WindowPlan:
             qc = torch.empty(self.n, 3, dtype=torch.int32, device=xyz.device)
             radial = torch.empty(self.n, dtype=torch.float32, device=xyz.device) if want_radial else None
             w = self.window_size
-            L.call('u2mkd_sptr_quant_coords', L.ptr(xyz), L.ptr(self.sort_idx), self.n, L.ptr(self.lo), w[0], w[1],
-                   w[2], q[0], q[1], q[2], L.ptr(qc), L.ptr(radial), L.stream())
+            if self.shift_win:       # (0.5 * window in fp32: the shift_size of sptr/modules.py:42)
+                sh = [float(np.float32(0.5) * np.float32(v)) for v in w]
+                L.call('u2mkd_sptr_quant_coords_shifted', L.ptr(xyz), L.ptr(self.sort_idx), self.n, L.ptr(self.lo), w[0], w[1],
+                       w[2], sh[0], sh[1], sh[2], q[0], q[1], q[2], L.ptr(qc), L.ptr(radial), L.stream())
+            else:
+                L.call('u2mkd_sptr_quant_coords', L.ptr(xyz), L.ptr(self.sort_idx), self.n, L.ptr(self.lo), w[0], w[1],
+                       w[2], q[0], q[1], q[2], L.ptr(qc), L.ptr(radial), L.stream())
             # host-known bound on the quantised coordinates of the affine axes (x, y and, in the cubic
             # branch, z): qc = floor((v mod w) / q) <= floor(w / q)
             axes = (0, 1) if want_radial else (0, 1, 2)
@@ -354,11 +374,53 @@ def window_attention(q, k, v, xyz, plan: WindowPlan, quant_size, quant_grid_leng
                                          int(quant_grid_length), float(split_a) if sphere else 0.0, span)
 
 
+class PlainAttentionFunction(Function):
+    """Table-free window attention (csrc/sptr_plain.hip): q, k, v [N, h, 16] fp32 (q pre-scaled), softmax over each token's window."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, plan):
+        L.require_cuda(q, k, v)
+        q, k, v = (t.contiguous().float() for t in (q, k, v))
+        n, h, d = q.shape
+        ctx.empty = h == 0 or n == 0
+        if ctx.empty:
+            ctx.shape = q.shape
+            return torch.zeros_like(q)
+        out = torch.empty_like(q)
+        lse = torch.empty(n, h, dtype=torch.float32, device=q.device)
+        L.call('u2mkd_sptr_plain_forward_strided', L.ptr(q), L.ptr(k), L.ptr(v), h * d, 1.0, L.ptr(plan.sort_idx), L.ptr(plan.wstart),
+               L.ptr(plan.wlen), n, h, d, L.ptr(out), h * d, L.ptr(lse), L.stream())
+        ctx.save_for_backward(q, k, v, out, lse)
+        ctx.plan = plan
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        if ctx.empty:
+            z = dout.new_zeros(ctx.shape)
+            return z, z, z, None
+        q, k, v, out, lse = ctx.saved_tensors
+        plan = ctx.plan
+        dout = dout.contiguous().float()
+        n, h, d = q.shape
+        delta = torch.empty(n, h, dtype=torch.float32, device=q.device)
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        L.call('u2mkd_sptr_plain_backward_strided', L.ptr(q), L.ptr(k), L.ptr(v), h * d, 1.0, L.ptr(out), L.ptr(dout), h * d,
+               L.ptr(lse), L.ptr(plan.sort_idx), L.ptr(plan.wstart), L.ptr(plan.wlen), n, h, d, L.ptr(delta), L.ptr(dq), L.ptr(dk),
+               L.ptr(dv), h * d, L.stream())
+        return dq, dk, dv, None
+
+
+def plain_window_attention(q, k, v, plan: WindowPlan):
+    """softmax over each token's window of q.k applied to v; q, k, v [N, h, 16] (q pre-scaled), no position tables."""
+    if q.dim() != 3 or q.shape[-1] != 16:
+        raise ValueError(f'window attention runs on [N, heads, 16] rows (head dim 16), got {tuple(q.shape)}')
+    return PlainAttentionFunction.apply(q, k, v, plan)
+
+
 def get_indices_params(xyz, batch, window_size, shift_win: bool):
     """sptr/utils.py:49-78 signature.  Returns (plan, inert, n_max, inert, inert, sort_idx)."""
-    if shift_win:
-        raise NotImplementedError('shift_win=True is never used by U2MKD (spherical_transformer.py:79)')
-    plan = WindowPlan(xyz, batch, window_size)
+    plan = WindowPlan(xyz, batch, window_size, shift_win=bool(shift_win))
     return plan, _Inert(), None, _Inert(), _Inert(), plan.sort_idx
 
 
@@ -366,12 +428,23 @@ def sparse_self_attention(query, key, value, xyz, index_0, index_0_offsets, n_ma
                           window_size, shift_win, pe_type='none', rel_query=False, rel_key=False, rel_value=False,
                           quant_size=None, quant_grid_length=None, relative_pos_query_table=None,
                           relative_pos_key_table=None, relative_pos_value_table=None, split_func=None):
-    """sptr/modules.py:11-66 signature; ``index_0`` must be the WindowPlan of get_indices_params."""
-    if not (pe_type == 'contextual' and rel_query and rel_key and rel_value):
-        raise NotImplementedError('only pe_type="contextual" with rel_query=rel_key=rel_value=True is on the '
-                                  'U2MKD path (core/models/nuscenes/spvcnn_spformer.py:70-72)')
+    """sptr/modules.py:11-66 signature; ``index_0`` must be the WindowPlan of get_indices_params.  pe_type 'contextual' with
+    rel_query = rel_key = rel_value = True and the three tables: the kernels of csrc/sptr.hip; no relative-position term at all
+    (any other pe_type, or 'contextual' with the three flags off): the table-free kernels of csrc/sptr_plain.hip; a subset of
+    the three terms is not implemented."""
+    rel = (bool(rel_query), bool(rel_key), bool(rel_value))
+    contextual = pe_type == 'contextual' and any(rel)
+    tables = (relative_pos_query_table, relative_pos_key_table, relative_pos_value_table)
+    if contextual and not (all(rel) and all(t is not None for t in tables)):
+        raise NotImplementedError('pe_type="contextual" runs with rel_query=rel_key=rel_value=True and all three tables '
+                                  '(core/models/nuscenes/spvcnn_spformer.py:70-72) or with none of them; a subset of the '
+                                  'relative-position terms has no kernel')
     if not isinstance(index_0, WindowPlan):
         raise TypeError('index_0 must come from u2mkd_amd.sptr.get_indices_params')
+    if bool(shift_win) != index_0.shift_win:
+        raise ValueError(f'shift_win={bool(shift_win)} but the window plan was built with shift_win={index_0.shift_win}')
+    if not contextual:
+        return plain_window_attention(query, key, value, index_0)
     split_a = None
     if split_func is not None:
         split_a = getattr(split_func, 'keywords', {}).get('a', 0.05 * 0.25)
