@@ -695,6 +695,51 @@ int u2mkd_ln_backward(const void *dy, const void *x, const void *ds /*may be NUL
                       float *partial /*[slabs,2,c]*/, float *dgamma /*[c]*/, float *dbeta /*[c]*/, void *dx,
                       void *db /*with w, else NULL*/, u2mkd_stream_t s);
 
+/* ---- reductions over the rows of each scene (csrc/gn.hip) -----------------------------------------------------------
+ * torchsparse.nn's GroupNorm, GlobalAvgPool and GlobalMaxPool over a SparseTensor: a SCENE is the set of rows whose batch
+ * index (the last coordinate column) is the same; its rows need not be contiguous.  torchsparse v1.4.0 runs these layers as a
+ * Python loop over the batch behind a host read of the batch size.
+ *   THE SCENE PLAN, built once per coordinate tensor:
+ *     bidx [n]            the batch index of every row; a row whose index is outside [0, nb) belongs to no scene (zeros out)
+ *     order [n], seg [nb + 1]   the rows grouped by scene, ascending row id inside a scene (a stable sort by batch index; rows
+ *                         with a negative index come first, in front of seg[0]), and the scenes' ranges in that order
+ *     slab_seg [nb + 1], slabs [nslab][4]   u2mkd_scene_slabs: every scene cut into slabs of at most 128 rows of its order,
+ *                         (scene, start in order, rows, 0) per slab, the scenes' ranges in that table; nslab =
+ *                         u2mkd_scene_num_slabs(n, nb) = ceil(n / 128) + nb is the table's capacity (0 if n or nb is 0), unused
+ *                         entries are (-1, 0, 0, 0).  16-byte aligned.  nb < 65536.
+ *   row_dtype             the dtype of the ROWS x, y, dy, dx [n, c]: 0 = fp32, 1 = bf16, 2 = fp16, anything else is an error;
+ *                         contiguous and 16-byte aligned.  c a multiple of 4 in 4..1024.  Statistics, parameters, their
+ *                         gradients, the pooled result and the pooled gradient dy [nb, c] are fp32.
+ *   u2mkd_gn_forward      F.group_norm per scene: per (scene, group) the mean and the BIASED variance over the (c / groups) x
+ *                         N_k elements, y = (x - mean) * rstd * gamma + beta.  groups divides c; c / groups need not be a multiple
+ *                         of 4.  gamma / beta may be NULL (affine=False).  partial: nslab * groups * 16 bytes (doubles).  mean, rstd
+ *                         [nb, groups] out (0, 0 for a scene without rows).  Three launches.
+ *   u2mkd_gn_backward     dx = rstd (g - s1 - xhat s2), g = dy * gamma, s1 = sum g / m, s2 = sum g xhat / m, m = (c / groups) N_k;
+ *                         dgamma [c] = sum_rows dy xhat, dbeta [c] = sum_rows dy (together or both NULL).  partial: nslab *
+ *                         (2 c + 2 groups) floats, sums: nb * groups * 2 floats (workspace).  Four launches.
+ *   u2mkd_scene_pool_forward   mode 0: out [nb, c] = the column mean per scene (NaN for a scene without rows), mode 1: the column
+ *                         max (-inf for a scene without rows; a NaN propagates) and arg [nb, c] = the row of the maximum, the
+ *                         smallest row id among equal maxima (-1 without rows).  partial: nslab * c * 8 bytes.  Two launches.
+ *   u2mkd_scene_pool_backward  mode 0: dx[row] = dy[b] / N_b; mode 1: dx = 0 except dy[b, ch] at row arg[b, ch].
+ * Every sum is carried in double and rounded once; no atomics and a fixed merge order: bitwise reproducible.  Nothing is
+ * launched on an error; n = 0 or nb = 0 returns 0 without a launch.  All launches go to the caller's stream.               */
+int64_t u2mkd_scene_num_slabs(int64_t n, int64_t nb);
+int u2mkd_scene_slabs(const int32_t *seg /*[nb+1]*/, int64_t nb, int64_t n, int32_t *slab_seg /*[nb+1]*/,
+                      int32_t *slabs /*[nslab,4]*/, int64_t nslab, u2mkd_stream_t s);
+int u2mkd_gn_forward(const void *x, int32_t row_dtype, int64_t n, int32_t c, int32_t groups, const int32_t *bidx,
+                     const int32_t *order, const int32_t *seg, const int32_t *slab_seg, const int32_t *slabs, int64_t nslab,
+                     int64_t nb, const float *gamma, const float *beta, float eps, void *partial, float *mean, float *rstd,
+                     void *y, u2mkd_stream_t s);
+int u2mkd_gn_backward(const void *dy, const void *x, int32_t row_dtype, int64_t n, int32_t c, int32_t groups, const int32_t *bidx,
+                      const int32_t *order, const int32_t *seg, const int32_t *slab_seg, const int32_t *slabs, int64_t nslab,
+                      int64_t nb, const float *mean, const float *rstd, const float *gamma, float *partial, float *sums,
+                      float *dgamma, float *dbeta, void *dx, u2mkd_stream_t s);
+int u2mkd_scene_pool_forward(const void *x, int32_t row_dtype, int64_t n, int32_t c, int32_t mode, const int32_t *order,
+                             const int32_t *seg, const int32_t *slab_seg, const int32_t *slabs, int64_t nslab, int64_t nb,
+                             void *partial, float *out, int32_t *arg, u2mkd_stream_t s);
+int u2mkd_scene_pool_backward(const float *dy, int32_t row_dtype, int64_t n, int32_t c, int32_t mode, const int32_t *bidx,
+                              const int32_t *seg, const int32_t *arg, int64_t nb, void *dx, u2mkd_stream_t s);
+
 /* ---- SphereFormer / sptr window attention ---------------------------------------
  * replaces the extern "C" launchers of third_party/SparseTransformer/src/sptr:
  *   precompute_all_cuda_launcher            (precompute/precompute_cuda_kernel.h)

@@ -117,6 +117,13 @@ SIGNATURES = {
     'u2mkd_ln_forward': (C.c_int, [_p, _i32, _i64, _i32, _p, _p, _f32, _p, _p, _p, _p]),
     'u2mkd_ln_add_forward': (C.c_int, [_p, _p, _p, _i32, _i64, _i32, _p, _p, _f32, _p, _p, _p, _p, _p]),
     'u2mkd_ln_backward': (C.c_int, [_p, _p, _p, _p, _i32, _i64, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    # reductions over the rows of each scene (csrc/gn.hip)
+    'u2mkd_scene_num_slabs': (_i64, [_i64, _i64]),
+    'u2mkd_scene_slabs': (C.c_int, [_p, _i64, _i64, _p, _p, _i64, _p]),
+    'u2mkd_gn_forward': (C.c_int, [_p, _i32, _i64, _i32, _i32, _p, _p, _p, _p, _p, _i64, _i64, _p, _p, _f32, _p, _p, _p, _p, _p]),
+    'u2mkd_gn_backward': (C.c_int, [_p, _p, _i32, _i64, _i32, _i32, _p, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    'u2mkd_scene_pool_forward': (C.c_int, [_p, _i32, _i64, _i32, _i32, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p]),
+    'u2mkd_scene_pool_backward': (C.c_int, [_p, _i32, _i64, _i32, _i32, _p, _p, _p, _i64, _p, _p]),
     'u2mkd_sptr_window_keys': (C.c_int, [_p, _p, _i64, _p, _p, _f32, _f32, _f32, _p, _p]),
     'u2mkd_select_mse_partials': (_i32, []),
     'u2mkd_select_mse_forward': (C.c_int, [_p, _p, _p, _i64, _i32, _p, _p, _p, _p]),

@@ -68,12 +68,7 @@ __device__ __forceinline__ void bn_acc_add_sq(BnAcc4 &a, const float4 &v, const 
     const double dx = (double)v.x - m.x, dy = (double)v.y - m.y, dz = (double)v.z - m.z, dw = (double)v.w - m.w;
     a.x += dx * dx; a.y += dy * dy; a.z += dz * dz; a.w += dw * dw;
 }
-// invstd = 1 / sqrt(v) rounded once: the fp32 estimate refined by one Newton step in double (relative error 1e-14 before the
-// rounding; every kernel that writes or uses an invstd takes it from here, so they agree bit for bit)
-__device__ __forceinline__ float bn_invstd(double v) {
-    const double r = (double)(1.f / sqrtf((float)v));
-    return (float)(r * (1.5 - 0.5 * v * r * r));
-}
+// (bn_invstd, the one rounding of 1 / sqrt: common.h -- csrc/gn.hip takes its rstd from it too)
 // running' = (1 - momentum) running + momentum s, from the stored (rounded) mean and M2, one rounding
 __device__ __forceinline__ void bn_running_update(float *rm, float *rv, float momentum, float mean, double unbiased) {
     const double mo = (double)momentum;

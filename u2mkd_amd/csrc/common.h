@@ -77,6 +77,13 @@ template <> __device__ __forceinline__ void st4<_Float16>(_Float16 *p, int64_t i
 }
 
 
+// invstd = 1 / sqrt(v) rounded once: the fp32 estimate refined by one Newton step in double (relative error 1e-14 before the
+// rounding; every kernel that writes or uses an invstd takes it from here, so they agree bit for bit)
+__device__ __forceinline__ float bn_invstd(double v) {
+    const double r = (double)(1.f / sqrtf((float)v));
+    return (float)(r * (1.5 - 0.5 * v * r * r));
+}
+
 // ---- hash table view (keys then values in one caller-owned buffer) --------
 struct TableView {
     int64_t *keys;   // cap entries, -1 = empty

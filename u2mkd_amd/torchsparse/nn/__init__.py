@@ -1,4 +1,5 @@
 from . import functional, utils
-from .modules import Conv3d, BatchNorm, ReLU, LeakyReLU
+from .modules import Conv3d, BatchNorm, ReLU, LeakyReLU, GroupNorm, GlobalAvgPool, GlobalMaxPool, SparseCrop
 
-__all__ = ['functional', 'utils', 'Conv3d', 'BatchNorm', 'ReLU', 'LeakyReLU']
+__all__ = ['functional', 'utils', 'Conv3d', 'BatchNorm', 'ReLU', 'LeakyReLU', 'GroupNorm', 'GlobalAvgPool', 'GlobalMaxPool',
+           'SparseCrop']

@@ -25,7 +25,7 @@ from ... import _host
 from ... import _lib as L
 from ..tensor import SparseTensor
 from ..utils import make_ntuple
-from .utils import get_kernel_offsets
+from .utils import fapply, get_kernel_offsets
 
 _HOST = False          # lib/_u2mkd_host.so (C++ host side of the hottest operators) once loaded; None: U2MKD_HOST_OPS=0
 
@@ -38,7 +38,8 @@ def host_ops():
 
 
 __all__ = ['sphash', 'sphashquery', 'spcount', 'spvoxelize', 'spdevoxelize', 'calc_ti_weights',
-           'spdownsample', 'conv3d', 'KernelMap', 'HashTable', 'ti_weights_n8', 'batch_norm']
+           'spdownsample', 'conv3d', 'KernelMap', 'HashTable', 'ti_weights_n8', 'batch_norm',
+           'group_norm', 'global_avg_pool', 'global_max_pool', 'spcrop', 'relu', 'leaky_relu']
 
 
 def _i32(t):
@@ -2123,3 +2124,220 @@ def add_layer_norm(shortcut, branch, row_scale, normalized_shape, weight, bias, 
         return stream, layer_norm(stream, normalized_shape, weight, bias, eps)
     return AddLayerNormFunction.apply(shortcut, branch, row_scale, weight, bias, eps,
                                       _ln_need(shortcut, branch, weight, bias))
+
+
+# ------------------------------------------------------- reductions over the rows of each scene
+# torchsparse.nn's GroupNorm, GlobalAvgPool, GlobalMaxPool (and SparseCrop, relu, leaky_relu) on SparseTensors.  The torchsparse
+# source is not at hand: the v1.4.0 semantics are RECALLED and defined through torch operators.
+# A SCENE = the rows whose batch index (coords[:, 3]) is the same; csrc/gn.hip.
+class ScenePlan:
+    """The rows of a coordinate tensor grouped by scene: ``bidx`` int32 [N], ``order`` int32 [N] (the rows by scene, ascending
+    row id inside a scene: a stable sort by batch index) / ``seg`` int32 [B + 1] (the scenes' ranges in it), and the slab table ``slab_seg`` [B + 1] / ``slabs`` [nslab, 4] that cuts every scene into
+    slabs of at most 128 rows of its order (u2mkd_scene_slabs).  ``nb`` = B = the largest batch index + 1."""
+    __slots__ = ('n', 'nb', 'bidx', 'order', 'seg', 'slab_seg', 'slabs', 'nslab')
+
+
+def scene_plan(coords):
+    """The :class:`ScenePlan` of ``coords`` [N, 4], cached on the coordinate tensor (``_plan``): B is read from the device ONCE
+    per coordinate tensor (``read_counts``); no layer or pass over the same tensor reads anything after that."""
+    def build():
+        c = _i32(coords)
+        p = ScenePlan()
+        p.n = c.shape[0]
+        p.bidx = c[:, 3].contiguous()
+        p.nb = int(read_counts([(p.bidx.max() + 1).clamp_(min=0)])[0]) if p.n else 0
+        dev = c.device
+        p.nslab = int(L.load().u2mkd_scene_num_slabs(p.n, p.nb))
+        if p.nslab == 0:
+            p.order = torch.zeros(p.n, dtype=torch.int32, device=dev)
+            p.seg = torch.zeros(p.nb + 1, dtype=torch.int32, device=dev)
+            p.slab_seg, p.slabs = p.seg, torch.zeros(1, 4, dtype=torch.int32, device=dev)
+            return p
+        # A stable sort by batch index, not _csr_by_destination: u2mkd_csr_build is made for many segments of a few entries
+        # (voxels); with B = 2 segments of 40 000 rows its per-segment sort of the entry ids runs in two workgroups and took
+        # 455 ms on an MI355X (NOTES N21.4).  Both are (order, seg) of the same grouping; neither reads anything back.
+        srt = torch.sort(p.bidx, stable=True)
+        p.order = srt.indices.int()
+        p.seg = torch.searchsorted(srt.values, torch.arange(p.nb + 1, dtype=torch.int32, device=dev)).int()
+        p.slab_seg = torch.empty(p.nb + 1, dtype=torch.int32, device=dev)
+        p.slabs = torch.empty(p.nslab, 4, dtype=torch.int32, device=dev)
+        L.call('u2mkd_scene_slabs', L.ptr(p.seg), p.nb, p.n, L.ptr(p.slab_seg), L.ptr(p.slabs), p.nslab, L.stream())
+        return p
+    return _plan(coords, 'scenes', build)
+
+
+_SCENE_MAX_C = 1024
+
+
+def _scene_rows(feats, *params):
+    """The dtype the scene kernels run the rows ``feats`` [N, C] in -- a stored 16-bit row type stays (``_stored16``), anything
+    else is fp32 --, or None: the loop formulation on torch operators (C % 4 != 0 or C > 1024, no rows, non-contiguous or
+    misaligned rows or parameters)."""
+    n, c = feats.shape
+    if n == 0 or c % 4 or c > _SCENE_MAX_C or not feats.is_contiguous() or feats.data_ptr() % 16 or not feats.is_floating_point():
+        return None
+    for p in params:
+        if p is not None and (not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous() or p.data_ptr() % 16):
+            return None
+    return _stored16(feats.dtype) or torch.float32
+
+
+def _scene_indices(plan):
+    """the row ids of every scene that has rows, for the loop formulation: [(k, index tensor)]"""
+    if plan.n == 0 or plan.nb == 0:
+        return []
+    seg = plan.seg.tolist()
+    order = plan.order.long()
+    return [(k, order[seg[k]:seg[k + 1]]) for k in range(plan.nb) if seg[k + 1] > seg[k]]
+
+
+def _group_norm_loop(feats, plan, num_groups, weight, bias, eps):
+    """the loop formulation (what torchsparse v1.4.0 runs): F.group_norm scene by scene"""
+    c = feats.shape[1]
+    out = torch.zeros_like(feats)
+    for _, idx in _scene_indices(plan):
+        # (torch.group_norm: the operator behind F.group_norm, whose Python wrapper refuses a scene of one row)
+        yk = torch.group_norm(feats[idx].t().reshape(1, c, -1), num_groups, weight, bias, eps, False)
+        out = out.index_copy(0, idx, yk.reshape(c, -1).t().to(out.dtype))
+    return out
+
+
+class GroupNormFunction(Function):
+    """F.group_norm per scene on the kernels of csrc/gn.hip: rows in ``run``, statistics, parameters and their gradients fp32"""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, plan, groups, eps, run):
+        xr = x.to(run)
+        n, c = xr.shape
+        dev = xr.device
+        y = torch.empty_like(xr)
+        partial = torch.empty(plan.nslab * groups * 2, dtype=torch.float64, device=dev)
+        mean = torch.empty(plan.nb, groups, dtype=torch.float32, device=dev)
+        rstd = torch.empty(plan.nb, groups, dtype=torch.float32, device=dev)
+        L.call('u2mkd_gn_forward', L.ptr(xr), _row_code(run), n, c, groups, L.ptr(plan.bidx), L.ptr(plan.order), L.ptr(plan.seg),
+               L.ptr(plan.slab_seg), L.ptr(plan.slabs), plan.nslab, plan.nb, L.ptr(gamma), L.ptr(beta), float(eps), L.ptr(partial),
+               L.ptr(mean), L.ptr(rstd), L.ptr(y), L.stream())
+        ctx.save_for_backward(xr, gamma, mean, rstd)
+        ctx.plan, ctx.groups, ctx.in_dtype, ctx.affine = plan, groups, x.dtype, (gamma is not None, beta is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        xr, gamma, mean, rstd = ctx.saved_tensors
+        plan, groups = ctx.plan, ctx.groups
+        n, c = xr.shape
+        dev = xr.device
+        dy = dy.contiguous().to(xr.dtype)
+        partial = torch.empty(plan.nslab * (2 * c + 2 * groups), dtype=torch.float32, device=dev)
+        sums = torch.empty(plan.nb * groups * 2, dtype=torch.float32, device=dev)
+        need = any(ctx.affine)
+        dgamma = torch.empty(c, dtype=torch.float32, device=dev) if need else None
+        dbeta = torch.empty(c, dtype=torch.float32, device=dev) if need else None
+        dx = torch.empty_like(xr)
+        L.call('u2mkd_gn_backward', L.ptr(dy), L.ptr(xr), _row_code(xr.dtype), n, c, groups, L.ptr(plan.bidx), L.ptr(plan.order),
+               L.ptr(plan.seg), L.ptr(plan.slab_seg), L.ptr(plan.slabs), plan.nslab, plan.nb, L.ptr(mean), L.ptr(rstd), L.ptr(gamma),
+               L.ptr(partial), L.ptr(sums), L.ptr(dgamma), L.ptr(dbeta), L.ptr(dx), L.stream())
+        if dx.dtype != ctx.in_dtype:
+            dx = dx.to(ctx.in_dtype)
+        return dx, (dgamma if ctx.affine[0] else None), (dbeta if ctx.affine[1] else None), None, None, None, None
+
+
+def group_norm_rows(feats, coords, num_groups, weight=None, bias=None, eps=1e-5):
+    """F.group_norm applied to the rows of every scene of (``feats`` [N, C], ``coords`` [N, 4]): for every batch index k,
+    ``out[b == k] = F.group_norm(feats[b == k].T.reshape(1, C, -1), G, weight, bias, eps)`` transposed back; a batch index
+    without rows contributes nothing.  Stored 16-bit rows come out in their type."""
+    L.require_cuda(feats, coords, weight, bias)
+    c = feats.shape[1]
+    if num_groups <= 0 or c % num_groups:
+        raise ValueError(f'group_norm: {num_groups} groups do not divide {c} channels')
+    plan = scene_plan(coords)
+    run = _scene_rows(feats, weight, bias)
+    if run is None or plan.nslab == 0:
+        return _group_norm_loop(feats, plan, num_groups, weight, bias, eps)
+    return GroupNormFunction.apply(feats, weight, bias, plan, num_groups, eps, run)
+
+
+def group_norm(input, num_groups, weight=None, bias=None, eps=1e-5):
+    """``group_norm_rows`` on a SparseTensor; coords, stride, cmaps and kmaps carried over as ``fapply`` does"""
+    return fapply(input, group_norm_rows, input.coords, num_groups, weight, bias, eps)
+
+
+class ScenePoolFunction(Function):
+    """the column mean (mode 0) or the column max (mode 1) of every scene's rows: dense [B, C]"""
+
+    @staticmethod
+    def forward(ctx, x, plan, mode, run):
+        xr = x.to(run)
+        n, c = xr.shape
+        dev = xr.device
+        out = torch.empty(plan.nb, c, dtype=torch.float32, device=dev)
+        arg = torch.empty(plan.nb, c, dtype=torch.int32, device=dev) if mode else None
+        partial = torch.empty(plan.nslab * c, dtype=torch.float64, device=dev)
+        L.call('u2mkd_scene_pool_forward', L.ptr(xr), _row_code(run), n, c, mode, L.ptr(plan.order), L.ptr(plan.seg),
+               L.ptr(plan.slab_seg), L.ptr(plan.slabs), plan.nslab, plan.nb, L.ptr(partial), L.ptr(out), L.ptr(arg), L.stream())
+        ctx.plan, ctx.mode, ctx.shape, ctx.run, ctx.in_dtype, ctx.arg = plan, mode, (n, c), run, x.dtype, arg
+        return out.to(x.dtype) if x.dtype != torch.float32 else out
+
+    @staticmethod
+    def backward(ctx, dy):
+        plan, (n, c) = ctx.plan, ctx.shape
+        dy = dy.float().contiguous()
+        dx = torch.empty(n, c, dtype=ctx.run, device=dy.device)
+        L.call('u2mkd_scene_pool_backward', L.ptr(dy), _row_code(ctx.run), n, c, ctx.mode, L.ptr(plan.bidx), L.ptr(plan.seg),
+               L.ptr(ctx.arg), plan.nb, L.ptr(dx), L.stream())
+        if dx.dtype != ctx.in_dtype:
+            dx = dx.to(ctx.in_dtype)
+        return dx, None, None, None
+
+
+def _scene_pool_loop(feats, plan, mode):
+    c = feats.shape[1]
+    rows = {k: (feats[idx].max(0).values if mode else feats[idx].mean(0)) for k, idx in _scene_indices(plan)}
+    empty = feats.new_full((c,), float('-inf') if mode else float('nan'))
+    return torch.stack([rows.get(k, empty) for k in range(plan.nb)]) if plan.nb else feats.new_zeros(0, c)
+
+
+def _scene_pool(input, mode):
+    feats, coords = input.feats, input.coords
+    L.require_cuda(feats, coords)
+    plan = scene_plan(coords)
+    run = _scene_rows(feats)
+    if run is None or plan.nslab == 0:
+        return _scene_pool_loop(feats, plan, mode)
+    return ScenePoolFunction.apply(feats, plan, mode, run)
+
+
+def global_avg_pool(input):
+    """dense [B, C]: per scene the column mean of its rows; a batch index without rows gives NaN (torch.mean of nothing)"""
+    return _scene_pool(input, 0)
+
+
+def global_max_pool(input):
+    """dense [B, C]: per scene the column max of its rows; a batch index without rows gives -inf, the identity (upstream, where
+    torch.max of nothing raises, would need a host read to do so); a NaN propagates; the gradient of a column goes to the
+    smallest row index among its maxima"""
+    return _scene_pool(input, 1)
+
+
+def spcrop(input, coords_min=None, coords_max=None):
+    """The rows with ``coords_min <= xyz <= coords_max`` on all three axes, both ends inclusive, as a new SparseTensor of the
+    same stride with fresh cmaps / kmaps.  Torch operations (a boolean mask): no kernel of its own."""
+    coords, feats = input.coords, input.feats
+    L.require_cuda(feats, coords)
+    mask = torch.ones(coords.shape[0], dtype=torch.bool, device=coords.device)
+    xyz = coords[:, :3]
+    if coords_min is not None:
+        mask &= (xyz >= torch.as_tensor(coords_min, dtype=coords.dtype, device=coords.device)).all(1)
+    if coords_max is not None:
+        mask &= (xyz <= torch.as_tensor(coords_max, dtype=coords.dtype, device=coords.device)).all(1)
+    return SparseTensor(feats=feats[mask], coords=coords[mask], stride=input.stride)
+
+
+def relu(input, inplace=True):
+    L.require_cuda(input.feats)
+    return fapply(input, torch.nn.functional.relu, inplace=inplace)
+
+
+def leaky_relu(input, negative_slope=0.1, inplace=True):
+    L.require_cuda(input.feats)
+    return fapply(input, torch.nn.functional.leaky_relu, negative_slope=negative_slope, inplace=inplace)

@@ -16,7 +16,7 @@ from ..utils import make_ntuple
 from . import functional as F
 from .utils import fapply
 
-__all__ = ['Conv3d', 'BatchNorm', 'ReLU', 'LeakyReLU']
+__all__ = ['Conv3d', 'BatchNorm', 'ReLU', 'LeakyReLU', 'GroupNorm', 'GlobalAvgPool', 'GlobalMaxPool', 'SparseCrop']
 
 
 class Conv3d(nn.Module):
@@ -79,3 +79,31 @@ class ReLU(nn.ReLU):
 class LeakyReLU(nn.LeakyReLU):
     def forward(self, input):
         return fapply(input, super().forward)
+
+
+class GroupNorm(nn.GroupNorm):
+    """nn.GroupNorm (same parameters and state-dict keys) over the rows of every scene of a SparseTensor: mean and biased
+    variance per (scene, group) over the (C / G) x N_k elements, on the scene kernels (F.group_norm)."""
+
+    def forward(self, input):
+        return F.group_norm(input, self.num_groups, self.weight, self.bias, self.eps)
+
+
+class GlobalAvgPool(nn.Module):
+    def forward(self, input):
+        return F.global_avg_pool(input)
+
+
+class GlobalMaxPool(nn.Module):
+    def forward(self, input):
+        return F.global_max_pool(input)
+
+
+class SparseCrop(nn.Module):
+    def __init__(self, coords_min=None, coords_max=None):
+        super().__init__()
+        self.coords_min = coords_min
+        self.coords_max = coords_max
+
+    def forward(self, input):
+        return F.spcrop(input, self.coords_min, self.coords_max)
