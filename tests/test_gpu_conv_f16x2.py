@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from conv_fwd_f64_ref import conv_f64 as _conv_f64
 from u2mkd_amd.synth import synth_batch
 
 pytestmark = pytest.mark.gpu
@@ -20,24 +21,6 @@ def F(hip):
 
 def _dev(x):
     return torch.from_numpy(np.ascontiguousarray(x)).cuda()
-
-
-def _conv_f64(x, w, nbr, flip):
-    """out[j] = sum_k x[nbr[k][j]] @ B_k in float64; forward: B_k = w[k] ([cin, cout]); input gradient (flip): the transposed
-    weights of the mirrored offset.  Also returns sum_k |x| @ |B_k| (the scale an error bound is relative to)."""
-    k, n = nbr.shape
-    xd, wd = x.double(), w.double()
-    cols = w.shape[1] if flip else w.shape[2]
-    out = torch.zeros(n, cols, dtype=torch.float64, device=x.device)
-    mag = torch.zeros_like(out)
-    for kk in range(k):
-        idx = nbr[kk].long()
-        ok = idx >= 0
-        rows = xd[idx.clamp(min=0)] * ok[:, None]
-        b = wd[k - 1 - kk].t() if flip else wd[kk]
-        out += rows @ b
-        mag += rows.abs() @ b.abs()
-    return out, mag
 
 
 def _run_tiles(L, lib, sch, x, w, flip, arith, n, k):
