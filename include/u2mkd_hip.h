@@ -415,6 +415,20 @@ int u2mkd_devoxelize_backward(const float *grad_out /*[n,c]*/, const int32_t *id
 int u2mkd_segment_sum(const float *src /*[*,c]*/, int32_t c, const int32_t *entry_row /*[E]*/,
                       const float *entry_w /*[E] or NULL*/, const int32_t *seg_offsets /*[nv+1]*/, int64_t nv,
                       int32_t mean, float *out /*[nv,c]*/, u2mkd_stream_t s);
+/* voxelize forward with the caller's counts: out[v] = sum_e src[row[e]] / counts[v], each term divided before it is added, in
+ * entry order; out[v] = 0 where counts[v] <= 0, whatever entries v has.  Where counts is the histogram of the index (every
+ * caller in the models) the result is that of u2mkd_segment_sum with mean != 0, bit for bit; where it is not, this is what
+ * torchsparse's voxelize_forward_cuda and u2mkd_voxelize_forward compute, and what u2mkd_voxelize_backward differentiates.
+ * The _bf16 / _f16 forms below: rows in and out of that type, as u2mkd_segment_sum_bf16 / _f16.                        */
+int u2mkd_segment_mean(const float *src /*[*,c]*/, int32_t c, const int32_t *entry_row /*[E]*/,
+                       const int32_t *seg_offsets /*[nv+1]*/, const int32_t *counts /*[nv]*/, int64_t nv,
+                       float *out /*[nv,c]*/, u2mkd_stream_t s);
+int u2mkd_segment_mean_bf16(const void *src /*bf16 [*,c]*/, int32_t c, const int32_t *entry_row /*[E]*/,
+                            const int32_t *seg_offsets /*[nv+1]*/, const int32_t *counts /*[nv]*/, int64_t nv,
+                            void *out /*bf16 [nv,c]*/, u2mkd_stream_t s);
+int u2mkd_segment_mean_f16(const void *src /*fp16 [*,c]*/, int32_t c, const int32_t *entry_row /*[E]*/,
+                           const int32_t *seg_offsets /*[nv+1]*/, const int32_t *counts /*[nv]*/, int64_t nv,
+                           void *out /*fp16 [nv,c]*/, u2mkd_stream_t s);
 /* The row movers of the point <-> voxel transfers on BF16 rows (BASELINE.json configs[4]; torchsparse's voxelize /
  * devoxelize functions cast to half under autocast like its conv): feature rows in and out are bf16 [., c], c a multiple
  * of 4, sums in fp32 in the same fixed order, one rounding at the store.  u2mkd_segment_sum_bf16 serves voxelize forward

@@ -1,4 +1,4 @@
-"""FP16 storage, the parts that need no GPU: the arith-5 fragment size, the eight _f16 entries next to their _bf16 twins and
+"""FP16 storage, the parts that need no GPU: the arith-5 fragment size, the nine _f16 entries next to their _bf16 twins and
 the row-dtype helper that routes the sparse operators under autocast."""
 import os
 import subprocess
@@ -11,7 +11,8 @@ from u2mkd_amd import _lib
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 F16_ENTRIES = ['u2mkd_conv_forward_tiles', 'u2mkd_conv_wgrad_pairs', 'u2mkd_conv_forward_pairs', 'u2mkd_linear_forward',
-               'u2mkd_pairs_gather_sum', 'u2mkd_voxelize_backward', 'u2mkd_devoxelize_forward', 'u2mkd_segment_sum']
+               'u2mkd_pairs_gather_sum', 'u2mkd_voxelize_backward', 'u2mkd_devoxelize_forward', 'u2mkd_segment_sum',
+               'u2mkd_segment_mean']
 
 
 def test_arith_5_fragments_have_the_size_of_arith_3():
@@ -100,3 +101,6 @@ def test_the_row_movers_keep_bf16_whatever_its_switch_says(monkeypatch):
     assert F._entry('u2mkd_segment_sum', torch.float32) == 'u2mkd_segment_sum'
     assert F._entry('u2mkd_segment_sum', torch.bfloat16) == 'u2mkd_segment_sum_bf16'
     assert F._entry('u2mkd_segment_sum', torch.float16) == 'u2mkd_segment_sum_f16'
+    assert F._entry('u2mkd_segment_mean', torch.float32) == 'u2mkd_segment_mean'
+    assert F._entry('u2mkd_segment_mean', torch.bfloat16) == 'u2mkd_segment_mean_bf16'
+    assert F._entry('u2mkd_segment_mean', torch.float16) == 'u2mkd_segment_mean_f16'

@@ -169,6 +169,9 @@ SIGNATURES = {
     'u2mkd_devoxelize_forward_f16': (C.c_int, [_p, _p, _p, _i64, _i32, _p, _p]),
     'u2mkd_segment_sum_bf16': (C.c_int, [_p, _i32, _p, _p, _p, _i64, _i32, _p, _p]),
     'u2mkd_segment_sum_f16': (C.c_int, [_p, _i32, _p, _p, _p, _i64, _i32, _p, _p]),
+    'u2mkd_segment_mean': (C.c_int, [_p, _i32, _p, _p, _p, _i64, _p, _p]),
+    'u2mkd_segment_mean_bf16': (C.c_int, [_p, _i32, _p, _p, _p, _i64, _p, _p]),
+    'u2mkd_segment_mean_f16': (C.c_int, [_p, _i32, _p, _p, _p, _i64, _p, _p]),
     'u2mkd_c2l_plan': (C.c_int, [_p, _p, _i32, _i64, _i32, _i32, _i32, _p, _p, _p]),
     'u2mkd_l2c_keys': (C.c_int, [_p, _p, _i32, _i64, _i32, _i64, _i64, _i32, _i32, _p, _p, _p, _p, _p]),
     'u2mkd_l2c_finish': (C.c_int, [_p, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p]),

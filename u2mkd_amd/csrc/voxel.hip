@@ -144,8 +144,8 @@ __global__ void devoxelize_bwd_kernel(const float *__restrict__ gout, const int3
 // (CSR built once per point<->voxel map), so there are no atomics, every output row is
 // written once, and the summation order is fixed.  One thread = 16 B of one output row.
 __global__ void segment_sum_kernel(const float *__restrict__ src, int c4, const int32_t *__restrict__ erow,
-                                   const float *__restrict__ ew, const int32_t *__restrict__ seg, int64_t nv,
-                                   int mean, float *__restrict__ out) {
+                                   const float *__restrict__ ew, const int32_t *__restrict__ seg,
+                                   const int32_t *__restrict__ counts, int64_t nv, int mean, float *__restrict__ out) {
     int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int64_t v = t / c4;
     if (v >= nv) return;
@@ -156,8 +156,15 @@ __global__ void segment_sum_kernel(const float *__restrict__ src, int c4, const 
     // mean: every term is divided by the segment length BEFORE it is added, in entry order -- the arithmetic
     // of torchsparse's voxelize (out[idx[i]] += feats[i] / counts[idx[i]]), so voxel means
     // (and with them the metric coordinates SphereFormer quantises into windows and relative-position bins)
-    // are bit-identical to the CPU path instead of differing in the last place
-    const float cnt = (float)(e1 - e0);
+    // are bit-identical to the CPU path instead of differing in the last place.  `counts` (mean only, may be null): the divisor
+    // is counts[v] as the caller passed it, not the segment length (the two agree when counts is the histogram of the index,
+    // and then so do the bits); a voxel whose count is 0 stays 0 whatever points it has, as in the atomic form
+    const int cv = (mean && counts) ? counts[v] : e1 - e0;
+    if (cv <= 0 && mean && counts) {
+        reinterpret_cast<float4 *>(out)[t] = acc;
+        return;
+    }
+    const float cnt = (float)cv;
     // four entries in flight (segments reach ~100 entries at stride 16: a one-at-a-time walk is a
     // chain of dependent L2 round trips); the accumulation order stays e0, e0+1, ...
     for (; e + 4 <= e1; e += 4) {
@@ -239,8 +246,8 @@ __global__ void devoxelize_fwd_rows_kernel(const T *__restrict__ feats, const in
 
 template <typename T>
 __global__ void segment_sum_rows_kernel(const T *__restrict__ src, int c4, const int32_t *__restrict__ erow,
-                                        const float *__restrict__ ew, const int32_t *__restrict__ seg, int64_t nv,
-                                        int mean, T *__restrict__ out) {
+                                        const float *__restrict__ ew, const int32_t *__restrict__ seg,
+                                        const int32_t *__restrict__ counts, int64_t nv, int mean, T *__restrict__ out) {
     int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int64_t v = t / c4;
     if (v >= nv) return;
@@ -248,7 +255,12 @@ __global__ void segment_sum_rows_kernel(const T *__restrict__ src, int c4, const
     const int e0 = seg[v], e1 = seg[v + 1];
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     int e = e0;
-    const float cnt = (float)(e1 - e0);
+    const int cv = (mean && counts) ? counts[v] : e1 - e0;      // (as in segment_sum_kernel)
+    if (cv <= 0 && mean && counts) {
+        st4(out, t, acc);
+        return;
+    }
+    const float cnt = (float)cv;
     for (; e + 4 <= e1; e += 4) {
         int r[4];
         float w[4];
@@ -503,8 +515,19 @@ int u2mkd_segment_sum(const float *src, int32_t c, const int32_t *entry_row, con
     U2_REQUIRE(c % 4 == 0, "u2mkd_segment_sum: c=%d must be a multiple of 4", c);
     int64_t total = nv * (c / 4);
     hipLaunchKernelGGL(segment_sum_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, as_stream(s), src, c / 4,
-                       entry_row, entry_w, seg_offsets, nv, mean, out);
+                       entry_row, entry_w, seg_offsets, (const int32_t *)nullptr, nv, mean, out);
     return check_launch("u2mkd_segment_sum");
+}
+
+int u2mkd_segment_mean(const float *src, int32_t c, const int32_t *entry_row, const int32_t *seg_offsets, const int32_t *counts,
+                       int64_t nv, float *out, u2mkd_stream_t s) {
+    if (nv == 0 || c == 0) return 0;
+    U2_REQUIRE(src && entry_row && seg_offsets && counts && out, "u2mkd_segment_mean: null pointer");
+    U2_REQUIRE(c % 4 == 0, "u2mkd_segment_mean: c=%d must be a multiple of 4", c);
+    int64_t total = nv * (c / 4);
+    hipLaunchKernelGGL(segment_sum_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, as_stream(s), src, c / 4,
+                       entry_row, (const float *)nullptr, seg_offsets, counts, nv, 1, out);
+    return check_launch("u2mkd_segment_mean");
 }
 
 }  // extern "C"
@@ -537,13 +560,15 @@ static int devoxelize_forward_rows(const char *who, const void *feats, const int
 
 template <typename T>
 static int segment_sum_rows(const char *who, const void *src, int32_t c, const int32_t *entry_row, const float *entry_w,
-                            const int32_t *seg_offsets, int64_t nv, int32_t mean, void *out, u2mkd_stream_t s) {
+                            const int32_t *seg_offsets, const int32_t *counts, int64_t nv, int32_t mean, void *out,
+                            u2mkd_stream_t s) {
     if (nv == 0 || c == 0) return 0;
     U2_REQUIRE(src && entry_row && seg_offsets && out, "%s: null pointer", who);
     U2_REQUIRE(c % 4 == 0, "%s: c=%d must be a multiple of 4", who, c);
     int64_t total = nv * (c / 4);
     hipLaunchKernelGGL(segment_sum_rows_kernel<T>, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, as_stream(s),
-                       reinterpret_cast<const T *>(src), c / 4, entry_row, entry_w, seg_offsets, nv, mean, reinterpret_cast<T *>(out));
+                       reinterpret_cast<const T *>(src), c / 4, entry_row, entry_w, seg_offsets, counts, nv, mean,
+                       reinterpret_cast<T *>(out));
     return check_launch(who);
 }
 
@@ -571,12 +596,24 @@ int u2mkd_devoxelize_forward_f16(const void *feats, const int32_t *idx, const fl
 
 int u2mkd_segment_sum_bf16(const void *src, int32_t c, const int32_t *entry_row, const float *entry_w,
                            const int32_t *seg_offsets, int64_t nv, int32_t mean, void *out, u2mkd_stream_t s) {
-    return segment_sum_rows<bf16row>("u2mkd_segment_sum_bf16", src, c, entry_row, entry_w, seg_offsets, nv, mean, out, s);
+    return segment_sum_rows<bf16row>("u2mkd_segment_sum_bf16", src, c, entry_row, entry_w, seg_offsets, nullptr, nv, mean, out, s);
+}
+
+int u2mkd_segment_mean_bf16(const void *src, int32_t c, const int32_t *entry_row, const int32_t *seg_offsets, const int32_t *counts,
+                          int64_t nv, void *out, u2mkd_stream_t s) {
+    U2_REQUIRE(counts || nv == 0 || c == 0, "u2mkd_segment_mean_bf16: null pointer");
+    return segment_sum_rows<bf16row>("u2mkd_segment_mean_bf16", src, c, entry_row, nullptr, seg_offsets, counts, nv, 1, out, s);
 }
 
 int u2mkd_segment_sum_f16(const void *src, int32_t c, const int32_t *entry_row, const float *entry_w,
                           const int32_t *seg_offsets, int64_t nv, int32_t mean, void *out, u2mkd_stream_t s) {
-    return segment_sum_rows<_Float16>("u2mkd_segment_sum_f16", src, c, entry_row, entry_w, seg_offsets, nv, mean, out, s);
+    return segment_sum_rows<_Float16>("u2mkd_segment_sum_f16", src, c, entry_row, entry_w, seg_offsets, nullptr, nv, mean, out, s);
+}
+
+int u2mkd_segment_mean_f16(const void *src, int32_t c, const int32_t *entry_row, const int32_t *seg_offsets, const int32_t *counts,
+                          int64_t nv, void *out, u2mkd_stream_t s) {
+    U2_REQUIRE(counts || nv == 0 || c == 0, "u2mkd_segment_mean_f16: null pointer");
+    return segment_sum_rows<_Float16>("u2mkd_segment_mean_f16", src, c, entry_row, nullptr, seg_offsets, counts, nv, 1, out, s);
 }
 
 int u2mkd_ti_weights(const float *coords, const int64_t *idx_kn, int64_t n, float scale, float *w_n8,

@@ -226,10 +226,16 @@ def _plan(t: torch.Tensor, name: str, build, *deps):
     return hit[1]
 
 
-def _segment_sum(src, erow, ew, seg, nv, mean):
-    """rows of src (fp32, bf16 or fp16: the output has the same type) summed per destination segment"""
+def _segment_sum(src, erow, ew, seg, nv, mean, counts=None):
+    """rows of src (fp32, bf16 or fp16: the output has the same type) summed per destination segment; ``counts`` (int32 [nv],
+    with ``mean``): the divisor of every segment, 0 = the row stays 0 (spvoxelize's ``counts`` as the caller passed it)"""
     c = src.shape[1]
     out = torch.empty(nv, c, dtype=src.dtype, device=src.device)
+    if counts is not None:
+        assert mean and ew is None
+        L.call(_entry('u2mkd_segment_mean', src.dtype), L.ptr(src), c, L.ptr(erow), L.ptr(seg), L.ptr(counts), nv, L.ptr(out),
+               L.stream())
+        return out
     L.call(_entry('u2mkd_segment_sum', src.dtype), L.ptr(src), c, L.ptr(erow),
            L.ptr(ew), L.ptr(seg), nv, int(mean), L.ptr(out), L.stream())
     return out
@@ -252,7 +258,7 @@ class VoxelizeFunction(Function):
         if c % 4 == 0:
             # deterministic scatter-mean: points grouped by voxel once per map, then a gather-sum
             order, seg = voxelize_plan(coords, nv)
-            out = _segment_sum(feats, order, None, seg, nv, True)
+            out = _segment_sum(feats, order, None, seg, nv, True, counts)
         else:
             out = torch.zeros(nv, c, dtype=torch.float32, device=feats.device)
             L.call('u2mkd_voxelize_forward', L.ptr(feats), L.ptr(coords), L.ptr(counts), n, nv, c, L.ptr(out),
