@@ -754,6 +754,47 @@ int u2mkd_scene_pool_forward(const void *x, int32_t row_dtype, int64_t n, int32_
 int u2mkd_scene_pool_backward(const float *dy, int32_t row_dtype, int64_t n, int32_t c, int32_t mode, const int32_t *bidx,
                               const int32_t *seg, const int32_t *arg, int64_t nb, void *dx, u2mkd_stream_t s);
 
+/* ---- bird's-eye-view operators (csrc/bev.hip) ------------------------------------------------------------------------
+ * torchsparse.nn's ToBEVReduction, ToBEVConvolution, ToDenseBEVConvolution and ToBEVHeightCompression.  coords int32 [n, 4] =
+ * (x, y, z, b), 16-byte aligned; dim in 0..2 is the height axis, the two other axes in ascending order are the BEV axes (bev0,
+ * bev1); every division truncates toward zero.
+ *   u2mkd_bev_plan        one pass over the coordinates.  Per row: keys[r] and hidx[r]; into block int32 [4] (zeroed by the call):
+ *                         block[0] = the rows that are out of range, block[1] = the largest batch index + 1.
+ *                           mode 0 (sparse result): keys[r] = the packed key (u2mkd_unpack_keys) of the row's coordinates with axis
+ *                             dim set to 0 and the BEV axes set to trunc(c / a) * a, a = (a0, a1, a2) > 0 the cell size per axis
+ *                             (1 leaves an axis as it is); out of range = not packable (|c| < 131072, 0 <= b < 512), key INT64_MAX.
+ *                           mode 1 (dense result [B, ., h, w]): keys[r] = (b * h + u) * w + v with u = trunc((c[bev0] - a[bev0]) /
+ *                             s[bev0]), v likewise on bev1, a = the OFFSET per axis; out of range = u outside 0..h-1, v outside
+ *                             0..w-1 or b < 0, key -1.
+ *                           hmode 0: hidx = 0.  hmode 1: hidx = trunc(c[dim] / s[dim]), the kernel index (no offset); outside
+ *                             0..nz-1 counts as out of range (stored as 0).  hmode 2 (mode 1 only): hidx = trunc((c[dim] - a[dim])
+ *                             / s[dim]) clamped to 0..nz-1, never out of range.
+ *   u2mkd_bev_tables      the neighbour tables of the convolution whose offset is the row's own height index: nbr [nk, n_out] =
+ *                         the row of group g at height k (-1: none), nbr_inv [nk, n_in] = group[r] at k = hidx[r], -1 elsewhere.
+ *                         group int32 [n_in] in 0..n_out-1; a (group, height) pair must hold at most one row.  Plain stores, no
+ *                         atomics; two launches.
+ *   u2mkd_bev_segment_mean  out[v] = the mean of src[order[e]] over seg[v] <= e < seg[v + 1], summed in double in entry order and
+ *                         rounded once to the row type (an empty segment gives 0).
+ *   u2mkd_bev_dense_store out [nb, c * z, h, w] (NCHW, every element written once: no memset, no atomics) from rows src [n_rows, c]:
+ *                         out[b][ch * z + q][u][v] = the fp32 sum, in ascending entry order, of src[order[e]][ch] over the entries
+ *                         of slot ((b * h + u) * w + v) * z + q (seg int32 [nb * h * w * z + 1], order int32 [n_rows]: the rows
+ *                         grouped by slot); seg = order = NULL: z = 1, n_rows = nb * h * w and row i IS cell i (a row-major [nb * h *
+ *                         w, c] tensor becomes NCHW).  1 <= z <= 32.
+ *   u2mkd_bev_dense_gather  the store's backward: dsrc[r][ch] = dout[b][ch * z + q][u][v] for every row r of slot (b, u, v, q).
+ *   row_dtype             0 = fp32, 1 = bf16, 2 = fp16: the type of the rows AND of the dense tensor; c a multiple of 4; both
+ *                         16-byte aligned.  Nothing is launched on an error.  All launches go to the caller's stream.            */
+int u2mkd_bev_plan(const int32_t *coords, int64_t n, int32_t dim, int32_t mode, int32_t hmode, int32_t s0, int32_t s1, int32_t s2,
+                   int32_t a0, int32_t a1, int32_t a2, int32_t h, int32_t w, int32_t nz, int64_t *keys /*[n]*/,
+                   int32_t *hidx /*[n]*/, int32_t *block /*[4]*/, u2mkd_stream_t s);
+int u2mkd_bev_tables(const int32_t *group, const int32_t *hidx, int64_t n_in, int64_t n_out, int32_t nk, int32_t *nbr,
+                     int32_t *nbr_inv, u2mkd_stream_t s);
+int u2mkd_bev_segment_mean(const void *src, int32_t row_dtype, int64_t n_src, int32_t c, const int32_t *order, const int32_t *seg,
+                           int64_t nv, void *out, u2mkd_stream_t s);
+int u2mkd_bev_dense_store(const void *src, int32_t row_dtype, int64_t n_rows, int32_t c, const int32_t *seg, const int32_t *order,
+                          int64_t nb, int32_t z, int32_t h, int32_t w, void *out, u2mkd_stream_t s);
+int u2mkd_bev_dense_gather(const void *dout, int32_t row_dtype, int64_t n_rows, int32_t c, const int32_t *seg, const int32_t *order,
+                           int64_t nb, int32_t z, int32_t h, int32_t w, void *dsrc, u2mkd_stream_t s);
+
 /* ---- SphereFormer / sptr window attention ---------------------------------------
  * replaces the extern "C" launchers of third_party/SparseTransformer/src/sptr:
  *   precompute_all_cuda_launcher            (precompute/precompute_cuda_kernel.h)

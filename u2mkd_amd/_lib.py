@@ -124,6 +124,12 @@ SIGNATURES = {
     'u2mkd_gn_backward': (C.c_int, [_p, _p, _i32, _i64, _i32, _i32, _p, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     'u2mkd_scene_pool_forward': (C.c_int, [_p, _i32, _i64, _i32, _i32, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p]),
     'u2mkd_scene_pool_backward': (C.c_int, [_p, _i32, _i64, _i32, _i32, _p, _p, _p, _i64, _p, _p]),
+    # bird's-eye-view operators (csrc/bev.hip)
+    'u2mkd_bev_plan': (C.c_int, [_p, _i64] + [_i32] * 12 + [_p, _p, _p, _p]),
+    'u2mkd_bev_tables': (C.c_int, [_p, _p, _i64, _i64, _i32, _p, _p, _p]),
+    'u2mkd_bev_segment_mean': (C.c_int, [_p, _i32, _i64, _i32, _p, _p, _i64, _p, _p]),
+    'u2mkd_bev_dense_store': (C.c_int, [_p, _i32, _i64, _i32, _p, _p, _i64, _i32, _i32, _i32, _p, _p]),
+    'u2mkd_bev_dense_gather': (C.c_int, [_p, _i32, _i64, _i32, _p, _p, _i64, _i32, _i32, _i32, _p, _p]),
     'u2mkd_sptr_window_keys': (C.c_int, [_p, _p, _i64, _p, _p, _f32, _f32, _f32, _p, _p]),
     'u2mkd_select_mse_partials': (_i32, []),
     'u2mkd_select_mse_forward': (C.c_int, [_p, _p, _p, _i64, _i32, _p, _p, _p, _p]),

@@ -39,7 +39,8 @@ def host_ops():
 
 __all__ = ['sphash', 'sphashquery', 'spcount', 'spvoxelize', 'spdevoxelize', 'calc_ti_weights',
            'spdownsample', 'conv3d', 'KernelMap', 'HashTable', 'ti_weights_n8', 'batch_norm',
-           'group_norm', 'global_avg_pool', 'global_max_pool', 'spcrop', 'relu', 'leaky_relu']
+           'group_norm', 'global_avg_pool', 'global_max_pool', 'spcrop', 'relu', 'leaky_relu',
+           'to_bev_reduction', 'to_bev_convolution', 'to_dense_bev_convolution', 'to_bev_height_compression']
 
 
 def _i32(t):
@@ -2347,3 +2348,265 @@ def relu(input, inplace=True):
 def leaky_relu(input, negative_slope=0.1, inplace=True):
     L.require_cuda(input.feats)
     return fapply(input, torch.nn.functional.leaky_relu, negative_slope=negative_slope, inplace=inplace)
+
+
+# ------------------------------------------------------- bird's-eye-view operators
+# torchsparse.nn's ToBEVReduction, ToBEVConvolution, ToDenseBEVConvolution and ToBEVHeightCompression (nn/modules/bev.py).  The
+# torchsparse source is not at hand: the v1.4.0 semantics are RECALLED; tests/bev_f64_ref.py states
+# them in float64.  ``dim`` is the height axis, the two other axes in ascending order are the BEV axes; every division truncates
+# toward zero.  csrc/bev.hip.
+_BEV_MAX_K = 31          # the offsets of a neighbour table the conv engine takes: a row's offsets are one int32 mask (u2mkd_kmap_rowmask)
+_BEV_MAX_Z = 32          # u2mkd_bev_dense_store: heights per cell
+
+
+class BevPlan:
+    """What the BEV operators derive from a coordinate tensor for one module geometry, built once (``bev_plan``):
+    ``n`` rows, ``nb`` = B, ``n_out`` output rows (sparse result) or cells B * H * W (dense), ``group`` int32 [n] the output row /
+    cell of every input row, ``hidx`` int32 [n] its height index, ``out_coords`` int32 [n_out, 4] (sparse result), ``order`` /
+    ``seg`` the input rows grouped by output row (by (cell, height) slot for the height compression), ``counts`` fp64 [n_out, 1]
+    the rows per output row, ``kmap`` the KernelMap of the convolution whose offset is the height index, or None: more than 31
+    heights, or a (cell, height) pair that holds several rows (the formulation on torch operators then)."""
+    __slots__ = ('n', 'nb', 'n_out', 'group', 'hidx', 'out_coords', 'order', 'seg', 'counts', 'kmap', 'nz')
+
+
+def bev_plan(coords, stride, dim, mode, hmode, a, h=0, w=0, nz=0):
+    """The :class:`BevPlan` of ``coords`` [N, 4] at tensor stride ``stride``, cached on the coordinate tensor per geometry
+    (``_plan``).  One launch of u2mkd_bev_plan writes keys, height indices and the flag / count block; the host reads that block
+    ONCE per (coordinate tensor, geometry) through ``read_counts`` -- the out-of-range count behind every ValueError, B, and the
+    number of (cell, height) pairs with more than one row -- and a second layer or step over the same tensor reads nothing.
+    mode 0: sparse result, ``a`` = cell size per axis; mode 1: dense result [B, ., h, w], ``a`` = offset per axis.  hmode 0: no
+    height index (reduction); 1: the kernel index trunc(c / s), checked against ``nz``; 2: the clamped height slot."""
+    if dim not in (0, 1, 2):
+        raise ValueError(f'dim={dim} must be 0, 1 or 2')
+    s = make_ntuple(stride, ndim=3)
+    a = tuple(int(v) for v in a)
+    name = 'bev_%s' % '_'.join(str(int(v)) for v in (dim, mode, hmode, *s, *a, h, w, nz))
+
+    def build():
+        c = _i32(coords).contiguous()
+        dev = c.device
+        p = BevPlan()
+        p.n, p.nz, p.kmap, p.out_coords = c.shape[0], nz, None, None
+        if p.n == 0:
+            p.nb = p.n_out = 0
+            p.group = p.hidx = p.order = torch.zeros(0, dtype=torch.int32, device=dev)
+            p.seg = torch.zeros(1, dtype=torch.int32, device=dev)
+            p.counts = torch.zeros(0, 1, dtype=torch.float64, device=dev)
+            if mode == 0:
+                p.out_coords = torch.zeros(0, 4, dtype=torch.int32, device=dev)
+            return p
+        keys = torch.empty(p.n, dtype=torch.int64, device=dev)
+        p.hidx = torch.empty(p.n, dtype=torch.int32, device=dev)
+        block = torch.empty(4, dtype=torch.int32, device=dev)
+        L.call('u2mkd_bev_plan', L.ptr(c), p.n, dim, mode, hmode, *s, *a, h, w, nz, L.ptr(keys), L.ptr(p.hidx), L.ptr(block),
+               L.stream())
+        if mode == 0:
+            uniq, inv = torch.unique(keys, return_inverse=True)      # sorted int64 == (b, x, y, z) lexicographic
+            cell = inv
+        else:
+            cell = keys
+        reads = [block[0:1], block[1:2]]
+        if hmode == 1:      # (cell, height) pairs that hold more than one row: the neighbour table has one slot per pair
+            srt = torch.sort(cell * nz + p.hidx).values
+            reads.append((srt[1:] == srt[:-1]).sum())
+        vals = read_counts(reads)
+        bad, p.nb, dup = vals[0], vals[1], (vals[2] if hmode == 1 else 0)
+        if bad:
+            what = ('height index outside 0..%d' % (nz - 1) if hmode == 1 else '')
+            where = ('BEV cell outside the %d x %d grid' % (h, w)) if mode == 1 else 'coordinates outside the packed key range'
+            raise ValueError('%d rows out of range: %s' % (bad, ' or '.join(v for v in (what, where) if v)))
+        if mode == 0:
+            p.n_out = uniq.shape[0]
+            p.out_coords = torch.empty(p.n_out, 4, dtype=torch.int32, device=dev)
+            L.call('u2mkd_unpack_keys', L.ptr(uniq), p.n_out, L.ptr(p.out_coords), L.stream())
+        else:
+            p.n_out = p.nb * h * w
+        p.group = cell.int()
+        if hmode == 2:
+            p.order, p.seg = _csr_by_destination(p.group * nz + p.hidx, p.n_out * nz)
+            p.counts = None
+            return p
+        p.order, p.seg = _csr_by_destination(p.group, p.n_out)
+        p.counts = (p.seg[1:] - p.seg[:-1]).double().unsqueeze(1)
+        if hmode == 1 and dup == 0 and nz <= _BEV_MAX_K:
+            nbr = torch.empty(nz, p.n_out, dtype=torch.int32, device=dev)
+            nbr_inv = torch.empty(nz, p.n, dtype=torch.int32, device=dev)
+            L.call('u2mkd_bev_tables', L.ptr(p.group), L.ptr(p.hidx), p.n, p.n_out, nz, L.ptr(nbr), L.ptr(nbr_inv), L.stream())
+            p.kmap = KernelMap(nbr, nbr_inv, p.n, p.n_out, False, p.out_coords)
+        return p
+    return _plan(coords, name, build)
+
+
+def _bev_run(feats):
+    """the dtype the BEV kernels run rows of ``feats`` in: a stored 16-bit row type stays, anything else is fp32"""
+    return _stored16(feats.dtype) or torch.float32
+
+
+def _pad4(rows):
+    pad = (-rows.shape[1]) % 4
+    return torch.nn.functional.pad(rows, (0, pad)) if pad else rows
+
+
+class BevMeanFunction(Function):
+    """the mean of the input rows of every output row (u2mkd_bev_segment_mean: summed in double, rounded once)"""
+
+    @staticmethod
+    def forward(ctx, x, plan, run):
+        c = x.shape[1]
+        xr = _pad4(x.to(run)).contiguous()
+        out = torch.empty(plan.n_out, xr.shape[1], dtype=run, device=x.device)
+        L.call('u2mkd_bev_segment_mean', L.ptr(xr), _row_code(run), plan.n, xr.shape[1], L.ptr(plan.order), L.ptr(plan.seg),
+               plan.n_out, L.ptr(out), L.stream())
+        ctx.plan, ctx.in_dtype = plan, x.dtype
+        return out if xr.shape[1] == c else out[:, :c].contiguous()
+
+    @staticmethod
+    def backward(ctx, g):
+        plan = ctx.plan
+        d = (g.float() / plan.counts.float()).index_select(0, plan.group.long())
+        return d.to(ctx.in_dtype), None, None
+
+
+class BevSumFunction(Function):
+    """fp32 rows summed per output row in ascending input-row order (u2mkd_segment_sum): the formulation on torch operators
+    ends in it instead of an index_add_, whose atomics would not give the same bits twice"""
+
+    @staticmethod
+    def forward(ctx, y, plan):
+        c = y.shape[1]
+        yr = _pad4(y.float()).contiguous()
+        out = _segment_sum(yr, plan.order, None, plan.seg, plan.n_out, False)
+        ctx.plan = plan
+        return out if yr.shape[1] == c else out[:, :c].contiguous()
+
+    @staticmethod
+    def backward(ctx, g):
+        return g.index_select(0, ctx.plan.group.long()), None
+
+
+class BevDenseFunction(Function):
+    """rows [n, C] -> dense [B, C * Z, H, W] (u2mkd_bev_dense_store) and its gather backward (u2mkd_bev_dense_gather);
+    ``seg`` / ``order`` None: the rows are the cells of a row-major [B * H * W, C] tensor"""
+
+    @staticmethod
+    def forward(ctx, rows, seg, order, nb, z, h, w, run):
+        c = rows.shape[1]
+        r = _pad4(rows.to(run)).contiguous()
+        cp = r.shape[1]
+        out = torch.empty(nb, cp * z, h, w, dtype=run, device=rows.device)
+        L.call('u2mkd_bev_dense_store', L.ptr(r), _row_code(run), r.shape[0], cp, L.ptr(seg), L.ptr(order), nb, z, h, w, L.ptr(out),
+               L.stream())
+        ctx.geom = (seg, order, nb, z, h, w, run, r.shape[0], c, cp, rows.dtype)
+        return out if cp == c else out[:, :c * z].contiguous()       # (c-major channels: the padding is at the end)
+
+    @staticmethod
+    def backward(ctx, g):
+        seg, order, nb, z, h, w, run, n, c, cp, in_dtype = ctx.geom
+        g = g.to(run)
+        if cp != c:
+            g = torch.nn.functional.pad(g, (0, 0, 0, 0, 0, (cp - c) * z))
+        g = g.contiguous()
+        d = torch.empty(n, cp, dtype=run, device=g.device)
+        L.call('u2mkd_bev_dense_gather', L.ptr(g), _row_code(run), n, cp, L.ptr(seg), L.ptr(order), nb, z, h, w, L.ptr(d), L.stream())
+        if cp != c:
+            d = d[:, :c]
+        return d.to(in_dtype), None, None, None, None, None, None, None
+
+
+def _bev_axes(dim):
+    return tuple(k for k in range(3) if k != dim)
+
+
+def to_bev_reduction(input, dim=1):
+    """The rows that share (b, the two BEV coordinates) become one row at height 0, their MEAN; stride unchanged.  Rows sorted by
+    (b, x, y, z), as spdownsample leaves them (upstream's coalesce() order is (x, y, z, b))."""
+    feats, coords = input.feats, input.coords
+    L.require_cuda(feats, coords)
+    plan = bev_plan(coords, input.stride, dim, 0, 0, (1, 1, 1))
+    if plan.n == 0:
+        return SparseTensor(feats=feats.new_zeros(0, feats.shape[1]), coords=plan.out_coords, stride=input.stride)
+    return SparseTensor(feats=BevMeanFunction.apply(feats, plan, _bev_run(feats)), coords=plan.out_coords, stride=input.stride)
+
+
+def _bev_conv_rows(feats, kernel, bias, plan):
+    """sum over the rows of every output row / cell of feats_r @ kernel[z_r] + bias: [n_out, Cout] in the row type of ``feats``"""
+    out_dtype = _stored16(feats.dtype) or feats.dtype
+    has_bias = isinstance(bias, torch.Tensor)
+    if plan.kmap is not None:
+        y = _conv_any_channels(feats, kernel, plan.kmap, False)
+        if has_bias:      # every input row brings the bias along: rows-of-the-cell times bias, added exactly and rounded once
+            y = (y.double() + plan.counts * bias.double().reshape(1, -1))
+        return y.to(out_dtype)
+    # more than 31 heights, or (cell, height) pairs with several rows (stride > 1): per-height matmuls, then the ordered row sum
+    x, k = feats.float(), kernel.float()
+    y = x.new_zeros(plan.n, k.shape[2])
+    for z in range(k.shape[0]):
+        y = y + (x * (plan.hidx == z).unsqueeze(1)) @ k[z]
+    if has_bias:
+        y = y + bias.float().reshape(1, -1)
+    return BevSumFunction.apply(y, plan).to(out_dtype)
+
+
+def _check_kernel(feats, kernel):
+    if kernel.dim() != 3 or feats.shape[1] != kernel.shape[1]:
+        raise RuntimeError(f'BEV convolution: rows of {feats.shape[1]} channels, kernel {tuple(kernel.shape)} is [n_kernels, Cin, Cout]')
+
+
+def to_bev_convolution(input, kernel, bias=0, stride=1, dim=1):
+    """y_r = feats_r @ kernel[trunc(c_r[dim] / s[dim])] + bias per input row, summed over the rows that share the output key
+    (axis ``dim`` 0, the BEV axes trunc(c / ratio) * ratio for stride > 1, ratio = s * stride on all three axes); the result has
+    stride ``ratio``.  A height index outside 0..n_kernels-1 raises ValueError."""
+    feats, coords = input.feats, input.coords
+    L.require_cuda(feats, coords, kernel, bias if isinstance(bias, torch.Tensor) else None)
+    _check_kernel(feats, kernel)
+    s = input.stride
+    ratio = tuple(int(s[k] * stride) for k in range(3))
+    cell = tuple(ratio[k] if (stride > 1 and k != dim) else 1 for k in range(3))
+    plan = bev_plan(coords, s, dim, 0, 1, cell, nz=kernel.shape[0])
+    if plan.n == 0:
+        return SparseTensor(feats=feats.new_zeros(0, kernel.shape[2]), coords=plan.out_coords, stride=ratio)
+    return SparseTensor(feats=_bev_conv_rows(feats, kernel, bias, plan), coords=plan.out_coords, stride=ratio)
+
+
+def _offset3(offset):
+    if isinstance(offset, torch.Tensor):
+        offset = offset.flatten().tolist()
+    return tuple(int(v) for v in list(offset)[:3])
+
+
+def to_dense_bev_convolution(input, kernel, bias=0, shape=None, offset=(0, 0, 0), dim=1):
+    """Dense [B, Cout, H, W], (H, W) = shape[BEV axes]: out[b, :, u, v] = the sum of feats_r @ kernel[trunc(c_r[dim] / s[dim])] +
+    bias over the rows with u = trunc((c[bev0] - offset[bev0]) / s[bev0]), v likewise; zero elsewhere.  u, v or the kernel index
+    out of range raise ValueError (upstream aliases the linear index silently)."""
+    feats, coords = input.feats, input.coords
+    L.require_cuda(feats, coords, kernel, bias if isinstance(bias, torch.Tensor) else None)
+    _check_kernel(feats, kernel)
+    b0, b1 = _bev_axes(dim)
+    h, w = int(shape[b0]), int(shape[b1])
+    plan = bev_plan(coords, input.stride, dim, 1, 1, _offset3(offset), h, w, kernel.shape[0])
+    cout = kernel.shape[2]
+    if plan.n == 0:
+        return feats.new_zeros(0, cout, h, w)
+    rows = _bev_conv_rows(feats, kernel, bias, plan)           # [B * H * W, Cout]: every cell is a row
+    return BevDenseFunction.apply(rows, None, None, plan.nb, 1, h, w, _bev_run(rows))
+
+
+def to_bev_height_compression(input, channels=None, shape=None, offset=(0, 0, 0), dim=1):
+    """Dense [B, C * Z, H, W], Z = shape[dim]: out[b, c * Z + w, u, v] = the sum of feats_r[c] over the rows of cell (u, v) whose
+    height slot clamp(trunc((c[dim] - offset[dim]) / s[dim]), 0, Z - 1) is w; u, v out of range raise ValueError."""
+    feats, coords = input.feats, input.coords
+    L.require_cuda(feats, coords)
+    c = feats.shape[1]
+    if channels is not None and channels != c:
+        raise RuntimeError(f'ToBEVHeightCompression: rows of {c} channels, the module expects {channels}')
+    b0, b1 = _bev_axes(dim)
+    h, w, z = int(shape[b0]), int(shape[b1]), int(shape[dim])
+    plan = bev_plan(coords, input.stride, dim, 1, 2, _offset3(offset), h, w, z)
+    if plan.n == 0:
+        return feats.new_zeros(0, c * z, h, w)
+    if z <= _BEV_MAX_Z:
+        return BevDenseFunction.apply(feats, plan.seg, plan.order, plan.nb, z, h, w, _bev_run(feats))
+    # more heights than the store's tile holds: upstream's formulation on torch operators
+    slot = plan.group.long() * z + plan.hidx.long()
+    dense = feats.new_zeros(plan.n_out * z, c, dtype=torch.float32).index_add_(0, slot, feats.float())
+    return dense.view(plan.nb, h, w, z, c).permute(0, 4, 3, 1, 2).reshape(plan.nb, c * z, h, w).to(feats.dtype)
