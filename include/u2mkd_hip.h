@@ -153,6 +153,16 @@ int u2mkd_conv_forward_sorted(const float *in, int64_t n_in, int32_t cin, const 
                               const int32_t *nbr_sorted /*[k,n_out]*/, const int32_t *order /*[n_out] or NULL*/,
                               const int32_t *tile_order /*[ceil(n_out/64)] or NULL*/, int64_t n_out, int32_t k,
                               int32_t kflip, float *out /*[n_out,cout]*/, u2mkd_stream_t s);
+/* LARGE KERNEL VOLUMES (csrc/conv_lk.hip; k = 5, k = 7, 3x3x5, k4s4): the same contraction for 1 <= k <= 343 on the table in
+ * NATURAL row order -- no row-mask sort, no tile schedule (both exist for k <= 31 only).  A workgroup owns 64 rows of the table
+ * and walks the offsets in chunks of 32, visiting only those its rows have; nbr is [k, ld] with ld >= n_rows (a slice of rows of
+ * a wider table); an index outside [0, n_in) counts as -1; kflip mirrors over the whole volume (k - 1 - offset).  fp32 rows only.
+ * Every element of out is written exactly once (a row without a neighbour: exact zeros), the same bits on every run;
+ * n_rows == 0 launches nothing.  u2mkd_conv_lk_supported: cin % 4 == 0, cout > 0, 1 <= k <= 343.                              */
+int32_t u2mkd_conv_lk_supported(int32_t cin, int32_t cout, int32_t k);
+int u2mkd_conv_forward_lk(const float *in /*[n_in,cin]*/, int64_t n_in, int32_t cin, const float *wt /*[k,cout,cin]*/,
+                          int32_t cout, const int32_t *nbr /*[k,ld]*/, int64_t ld, int64_t n_rows, int32_t k, int32_t kflip,
+                          float *out /*[n_rows,cout]*/, u2mkd_stream_t s);
 /* The TILE-LOCAL PAIR schedule (csrc/conv_tp.hip), for layers whose reduction fits the register
  * file (u2mkd_conv_tiles_supported: cin in {32,64,96,128}, cout in {32,64,96,128}): the (row,
  * neighbour) pairs of a 64-row tile are compacted per offset in LDS with wave ballots + prefix

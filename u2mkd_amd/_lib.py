@@ -40,6 +40,8 @@ SIGNATURES = {
     'u2mkd_conv_forward': (C.c_int, [_p, _i64, _i32, _p, _i32, _p, _i64, _i32, _i32, _p, _p]),
     'u2mkd_conv_forward_sorted': (C.c_int, [_p, _i64, _i32, _p, _i32, _p, _p, _p, _i64, _i32, _i32, _p, _p]),
     'u2mkd_debug_conv_forward_sorted': (C.c_int, [_p, _i64, _i32, _p, _i32, _p, _p, _p, _i64, _i32, _i32, _i32, _p, _p]),
+    'u2mkd_conv_lk_supported': (_i32, [_i32, _i32, _i32]),
+    'u2mkd_conv_forward_lk': (C.c_int, [_p, _i64, _i32, _p, _i32, _p, _i64, _i64, _i32, _i32, _p, _p]),
     'u2mkd_stream_wait_stream': (C.c_int, [_p, _p]),
     'u2mkd_sgd_chunk_elements': (_i32, []),
     'u2mkd_sgd_batch': (C.c_int, [_p, _i32, _i64, _f32, _f32, _f32, _i32, _i32, _p]),

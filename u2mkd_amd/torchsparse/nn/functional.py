@@ -876,6 +876,9 @@ class PairSchedule:
 KMAP_USES = {}
 
 
+_WGRAD_BLOCK = 64        # offsets per weight-gradient plan (u2mkd_wgrad_plan: one wave of 64 lanes)
+
+
 class KernelMap:
     """Kernel map of one (tensor_stride, kernel_size, stride, dilation) key.
 
@@ -896,6 +899,7 @@ class KernelMap:
         self.out_coords = out_coords
         self._rulebook = None
         self._pairs = None
+        self._pair_blocks = None
         self._sorted = {}
         self._pair_schedule = None
         self.tag = None          # (network tag, map key): set by prefetch_kmaps(tag=...), see KMAP_USES
@@ -914,7 +918,7 @@ class KernelMap:
             if use == 'pair_schedule':
                 self.pair_schedule()
             elif use == 'pairs_plan':
-                self.pairs_plan()
+                self.pairs_blocks()
             elif use[0] == 'schedule' and (not use[1] or self.nbr_inv is not None):
                 self.schedule(use[1])
 
@@ -943,6 +947,9 @@ class KernelMap:
         the compacted rulebook plus the device-side work split of the weight-gradient
         kernel.  Built without any host synchronisation: the pair buffer is sized by
         the upper bound K * n_out and only its first P rows are meaningful."""
+        if self.k > _WGRAD_BLOCK:
+            raise RuntimeError(f'KernelMap.pairs_plan: kernel volume {self.k} above {_WGRAD_BLOCK}: the weight gradient takes its offsets in '
+                               'blocks (KernelMap.pairs_blocks)')
         if self._pairs is None:
             self._note('pairs_plan')
             k, n_out = self.k, self.n_out
@@ -961,9 +968,46 @@ class KernelMap:
             self._pairs = (pairs, nbsizes, plan)
         return self._pairs
 
+    def pairs_blocks(self):
+        """[(b0, b1, pairs, nbsizes, plan)]: ``pairs_plan`` per block of at most 64 offsets -- u2mkd_wgrad_plan is one wave of 64
+        lanes.  ``nbr`` is [K, n_out], so offsets b0 .. b1 are a contiguous slice of it and a block is the compacted rulebook and
+        the work split of that slice; up to 64 offsets there is one block, ``pairs_plan`` itself.  No host synchronisation."""
+        if self._pair_blocks is not None:
+            return self._pair_blocks[0]
+        if self.k <= _WGRAD_BLOCK:
+            self._pair_blocks = ([(0, self.k) + self.pairs_plan()], self._pairs[1])
+        else:
+            self._note('pairs_plan')
+            n_out = self.n_out
+            dev = self.nbr.device
+            nblocks = max((n_out + 1023) // 1024, 1)
+            lib, st = L.load(), L.stream()
+            nbsizes_all = torch.zeros(self.k, dtype=torch.int32, device=dev)
+            blocks = []
+            for b0 in range(0, self.k, _WGRAD_BLOCK):
+                b1 = min(b0 + _WGRAD_BLOCK, self.k)
+                kb = b1 - b0
+                tbl, nbsizes = self.nbr[b0:b1], nbsizes_all[b0:b1]
+                block_counts = torch.empty(kb, nblocks, dtype=torch.int32, device=dev)
+                cap = max(min(kb * n_out, self.n_in * kb), 1)
+                pairs = torch.empty(cap, 2, dtype=torch.int32, device=dev)
+                plan = torch.empty(lib.u2mkd_wgrad_plan_ints(kb), dtype=torch.int32, device=dev)
+                if n_out:
+                    L.call('u2mkd_kmap_sizes', L.ptr(tbl), n_out, kb, L.ptr(nbsizes), L.ptr(block_counts), st)
+                    L.call('u2mkd_kmap_compact', L.ptr(tbl), n_out, kb, L.ptr(nbsizes), L.ptr(block_counts), L.ptr(pairs), st)
+                L.call('u2mkd_wgrad_plan', L.ptr(nbsizes), kb, n_out, L.ptr(plan), st)
+                blocks.append((b0, b1, pairs, nbsizes, plan))
+            self._pair_blocks = (blocks, nbsizes_all)
+        return self._pair_blocks[0]
+
     def rulebook(self):
         """torchsparse's (nbmaps [P,2], nbsizes [K]); trimming to P is the only host sync."""
         if self._rulebook is None:
+            if self.k > _WGRAD_BLOCK:       # the blocks' rulebooks one after the other: offsets ascending, as v1.4.0 lists them
+                blocks = self.pairs_blocks()
+                totals = torch.stack([b[4][0] for b in blocks]).tolist()
+                self._rulebook = (torch.cat([b[2][:t] for b, t in zip(blocks, totals)]), self._pair_blocks[1])
+                return self._rulebook
             pairs, nbsizes, plan = self.pairs_plan()
             total = int(plan[0].item())
             self._rulebook = (pairs[:total], nbsizes)
@@ -1054,6 +1098,8 @@ def _conv_os(feats, weight, transpose, cout, kmap, inverse, n_rows, kflip, epilo
     gradient of a symmetric (submanifold) map computed on the forward table with mirrored offsets -- in the
     pair schedule that is simply the swapped-role walk."""
     out = torch.empty(n_rows, cout, dtype=feats.dtype, device=feats.device)
+    if kmap.k > _PAIRS_MAX_K:                    # the pair schedule's scratch is K * n * cout * 4 bytes: every call on the offset-chunk kernel
+        return _conv_lk(feats, weight, transpose, cout, kmap, inverse, n_rows, kflip, out)
     rows16 = feats.dtype != torch.float32        # (ConvolutionFunction hands fp32, bf16 or fp16 rows)
     if rows16 and not L.load().u2mkd_conv_tiles_supported(feats.shape[1], cout, kmap.k):
         # bf16 / fp16 storage, every shape the tile kernel has no instantiation for (_conv_rows16_ok: multiples of 32)
@@ -1064,6 +1110,8 @@ def _conv_os(feats, weight, transpose, cout, kmap, inverse, n_rows, kflip, epilo
         f2 = x3 and _pairs_f16x2(feats.shape[1], cout)          # the same kernel in f16x2 arithmetic (arith-4 fragments)
         wt = _weight_layout(weight, transpose, x3, arith=4 if f2 else 0)
         return kmap.pair_schedule().run(feats, wt, cout, bool(inverse) or bool(kflip), out, fragments=2 if f2 else x3, epilogue=epilogue)
+    if kmap.k > _TILES_MAX_K:                 # no row mask, no tile schedule beyond 31 offsets
+        return _conv_lk(feats, weight, transpose, cout, kmap, inverse, n_rows, kflip, out)
     if inverse and kmap.nbr_inv is None:      # symmetric map: the inverse table is the mirrored forward table
         inverse, kflip = False, 1 - int(kflip)
     sch = kmap.schedule(inverse)
@@ -1071,10 +1119,47 @@ def _conv_os(feats, weight, transpose, cout, kmap, inverse, n_rows, kflip, epilo
     return sch.run(feats, weight, transpose, cout, kflip, out, epilogue=epilogue)
 
 
+_TILES_MAX_K = 31        # a row's offsets are one int32 mask (u2mkd_kmap_rowmask): the tile schedule and the tile kernels
+_PAIRS_MAX_K = 64        # beyond: every forward / input gradient on the offset-chunk kernel, on fp32 rows
+_LK_MAX_K = 343          # u2mkd_conv_lk_supported: 7 x 7 x 7
+
+
+def _lk_route(cin, cout, k, n_rows, rows16=False):
+    """True where _conv_os sends an fp32-row launch to the offset-chunk kernel (csrc/conv_lk.hip)"""
+    return k > _PAIRS_MAX_K or (k > _TILES_MAX_K and not rows16 and not _pairs_mode(cin, cout, n_rows))
+
+
+def _conv_lk(feats, weight, transpose, cout, kmap, inverse, n_rows, kflip, out):
+    """_conv_os on u2mkd_conv_forward_lk: the (inverse) table in natural row order, the offsets in chunks of 32; a symmetric map's
+    inverse roles on the forward table with mirrored offsets.  fp32 rows; the weights row-major as TileSchedule.run's
+    non-fragment path passes them."""
+    if feats.dtype != torch.float32:
+        raise RuntimeError(f'conv3d: kernel volume {kmap.k} on {feats.dtype} rows: the offset-chunk kernel takes fp32 rows')
+    if inverse and kmap.nbr_inv is None:
+        inverse, kflip = False, 1 - int(kflip)
+    tbl = kmap.nbr_inv if inverse else kmap.nbr
+    assert tbl.shape[1] == n_rows
+    n_in, cin = feats.shape
+    wt = _weight_layout(weight, transpose, False)
+    L.call('u2mkd_conv_forward_lk', L.ptr(feats), n_in, cin, L.ptr(wt), cout, L.ptr(tbl), n_rows, n_rows, kmap.k, int(kflip),
+           L.ptr(out), L.stream())
+    return out
+
+
+def _rows16_volume_ok(cin, cout, k):
+    """16-bit rows at kernel volume k: every volume the tile schedule takes; 32 .. 64 offsets where the pair schedule runs the
+    layer (the tile kernel's shapes would need the row mask); above 64 the layer computes on fp32 rows and rounds once."""
+    if k <= _TILES_MAX_K:
+        return True
+    return k <= _PAIRS_MAX_K and not L.load().u2mkd_conv_tiles_supported(cin, cout, k)
+
+
 def conv_epilogue_supported(feats, cin, cout, k, n_rows):
     """True where conv_eval_affine can fold the affine into the convolution's store: fp32 rows on the tile-pair kernel
     (u2mkd_conv_forward_tiles_ep) or on the pair schedule (u2mkd_pairs_gather_sum_ep)."""
     if feats.dtype != torch.float32 or row_dtype() is not None or cin % 4 or cout % 4:
+        return False
+    if _lk_route(cin, cout, k, n_rows):           # the offset-chunk kernel has no folded store: conv, then BatchNorm
         return False
     if _pairs_mode(cin, cout, n_rows):
         return True
@@ -1609,7 +1694,7 @@ class ConvolutionFunction(Function):
         # custom_fwd(cast_inputs=half); shapes without a 16-bit kernel (the 4-channel stem) compute on fp32 rows and round the
         # result once
         want16 = row_dtype()
-        rows16 = want16 if _conv_rows16_ok(cin, cout) else None
+        rows16 = want16 if _conv_rows16_ok(cin, cout) and _rows16_volume_ok(cin, cout, k) else None
         ctx.in_dtype = input.dtype
         input = _rows(input, rows16)
         if input.shape[1] != cin:
@@ -1645,16 +1730,20 @@ class ConvolutionFunction(Function):
         side, deferred_join = None, False
         if do_w:
             # dW[k] = sum over the offset's pairs of X[in]^T dY[out] (transposed conv: roles swapped)
-            pairs, _, plan = kmap.pairs_plan()
+            # (above 64 offsets: one launch per block of 64, each into its slice grad_weight[b0:b1]; the launches follow each
+            # other on one stream and share the workspace)
+            blocks = kmap.pairs_blocks()
             lib = L.load()
-            nbytes = lib.u2mkd_conv_wgrad_pairs_workspace_bytes(kmap.n_out, cin, cout, k)
+            nbytes = lib.u2mkd_conv_wgrad_pairs_workspace_bytes(kmap.n_out, cin, cout, min(k, _WGRAD_BLOCK))      # (the widest block)
             ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=g.device)
             grad_weight = torch.empty_like(weight)
-            side, deferred_join = _wgrad_side(weight, ctx.weight_is_param, g.device, do_x, input, g, ws, grad_weight, pairs, plan,
+            used = (blocks[0][2], blocks[0][4]) if len(blocks) == 1 else [t for b in blocks for t in (b[2], b[4])]
+            side, deferred_join = _wgrad_side(weight, ctx.weight_is_param, g.device, do_x, input, g, ws, grad_weight, *used,
                                                allow=getattr(ctx, 'overlap_ok', True))
             st = side.cuda_stream if side is not None else L.stream()
-            L.call(_entry('u2mkd_conv_wgrad_pairs', input.dtype), L.ptr(input), cin, L.ptr(g), cout,
-                   L.ptr(pairs), L.ptr(plan), kmap.n_out, k, 1 if transposed else 0, L.ptr(ws), nbytes, L.ptr(grad_weight), st)
+            for b0, b1, pairs, _, plan in blocks:
+                L.call(_entry('u2mkd_conv_wgrad_pairs', input.dtype), L.ptr(input), cin, L.ptr(g), cout, L.ptr(pairs), L.ptr(plan),
+                       kmap.n_out, b1 - b0, 1 if transposed else 0, L.ptr(ws), nbytes, L.ptr(grad_weight[b0:b1]), st)
         if do_x:
             # dX[i] = sum_k dY[out_k(i)] @ W[k]^T : same kernel on the swapped-role table,
             # B_k = W[k] read as [cin][cout] (reduction over cout contiguous).
@@ -1708,6 +1797,9 @@ def conv3d(input: SparseTensor, weight: torch.Tensor, kernel_size, bias=None, st
             if bias is not None:
                 feats = feats + bias
         output = SparseTensor(coords=coords, feats=feats, stride=input.stride)
+    elif kernel_size[0] * kernel_size[1] * kernel_size[2] > _LK_MAX_K:
+        raise ValueError('conv3d: kernel volume %d (kernel_size %s) above %d' % (kernel_size[0] * kernel_size[1] * kernel_size[2],
+                                                                                   kernel_size, _LK_MAX_K))
     elif not transposed:
         key = (input.stride, kernel_size, stride, dilation)
         kmap = input.kmaps.get(key)
