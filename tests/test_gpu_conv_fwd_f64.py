@@ -523,3 +523,88 @@ def test_conv_eval_affine_matches_the_float64_epilogue(L, F, c, kind, res):
     bd = R.epilogue_bound(R.bound(fam[1], mag, r), emag, scale, res)
     _judge('conv_eval_affine %s %s' % (kind, fam[0][6:]), (c, c), 'scene', role, 'rows', out.F, want, bd, mag, r,
            dead_value=_dead_value(shift, resid, True, n_y), emag=emag)
+
+
+# ---- the dense route: LinearFunction and PointwiseConvFunction -------------------------------------------------------------------
+
+_DENSE_KIND = {'u2mkd_linear_forward': 'f32', 'u2mkd_linear_forward_x3': 'x3', 'u2mkd_linear_forward_f16x2': 'f16x2',
+               'u2mkd_linear_forward_bf16': 'tile16', 'u2mkd_linear_forward_f16': 'tile16'}      # (16-bit: ONE rounding, at the store)
+_DENSE_ROWS = 65                  # the smallest size that crosses a 64-row tile and leaves a one-row tail
+_DENSE_CASES = [(fn, (64, 64), dt) for fn in ('linear', 'pointwise') for dt in (F32, BF16, F16)] + [('linear', (36, 20), F32)]
+
+
+@pytest.mark.parametrize('fn,shape,dtype', _DENSE_CASES, ids=lambda v: str(v).replace('torch.', ''))
+def test_linear_and_pointwise_conv_launch_the_dense_route(L, F, fn, shape, dtype):
+    """LinearFunction / PointwiseConvFunction at 65 rows: the forward launches the entry _dense_route names, the backward ONE
+    u2mkd_conv_wgrad_pairs[_bf16|_f16] and then the input gradient's entry (36 -> 20, no fragment shape: u2mkd_transpose_weights,
+    then u2mkd_linear_forward); y and x.grad against float64 x @ W under the bound of the arithmetic the route names (a linear
+    layer is the one-offset identity table), w.grad under wgrad_f64_ref's."""
+    import wgrad_f64_ref as W
+    cin, cout = shape
+    n = _DENSE_ROWS
+    nbr = torch.arange(n, dtype=torch.int32, device='cuda')[None]
+    w = R.make_weights(1, cin, cout, 'unit', seed=9).cuda()                     # kernel layout [1, cin, cout]
+    x = R.make_rows('unit', n, cin, dtype, 31).cuda().float().requires_grad_(True)
+    g = R.make_rows('unit', n, cout, dtype, 32).cuda().float()
+    wp = (w[0].t().contiguous() if fn == 'linear' else w[0].clone()).requires_grad_(True)       # nn.Linear: [out, in]
+    apply = (lambda: F.LinearFunction.apply(x, wp, None)) if fn == 'linear' else (lambda: F.PointwiseConvFunction.apply(x, wp, None))
+    with _Spy(L) as spy:
+        if dtype == F32:
+            y = apply()
+        else:
+            with torch.autocast('cuda', dtype=dtype):
+                y = apply()
+        _sync('%s forward' % fn)
+        fwd, spy.names = [e for e in spy.names if 'weight_fragments' not in e], []
+        y.backward(g.to(y.dtype))
+        _sync('%s backward' % fn)
+        bwd = [e for e in spy.names if 'weight_fragments' not in e and 'wgrad_plan' not in e]
+    assert y.dtype == dtype and x.grad.dtype == F32
+    rf, rb = F._dense_route(dtype, cin, cout), F._dense_route(dtype, cout, cin)
+    assert fwd == [rf.entry], (fwd, rf)
+    assert bwd == ['u2mkd_conv_wgrad_pairs' + TAG.get(dtype, '')] + ([] if rb.fragments else ['u2mkd_transpose_weights']) + [rb.entry], (bwd, rb)
+    if shape == (36, 20):
+        assert (rf.entry, rb.entry) == ('u2mkd_linear_forward', 'u2mkd_linear_forward') and not rf.fragments
+    xs, gs = x.detach().to(dtype), g.to(dtype)
+    for what, route, got, src, role in (('forward', rf, y.detach(), xs, 'fwd'), ('x.grad', rb, x.grad.to(dtype), gs, 'fwdT')):
+        ref, mag, part, r = _reference(src, w, nbr, n, role, dtype)
+        bd = R.bound(_DENSE_KIND[route.entry], mag, r, ref, part, dtype if dtype != F32 else None, 1)
+        _judge('%s %s %s' % (fn, what, route.entry[6:]), shape, 'identity', role, 'unit', got, ref, bd, mag, r)
+    # w.grad: dW = X^T dY in the kernel layout (nn.Linear: its transpose), fp32 whatever the rows
+    pairs = torch.stack([nbr[0], nbr[0]], 1).contiguous()
+    dw, mag = W.wgrad_f64(xs, gs, pairs, [n], 0)
+    r = W.rel_err(W.honest_fp32(xs, gs, pairs, [n], 0), dw, mag)
+    got = (wp.grad.t() if fn == 'linear' else wp.grad)[None]
+    t = W.T_X3 if (dtype == F32 and W.family(cin, cout, dtype)[0] == 'x3') else W.T_EXACT
+    ok, over, rel = W.check(got, dw, mag, t, r)
+    print('[conv-f64] %s w.grad %dx%d: err/mag 2^%.1f  err/bound %.3f' % (fn, cin, cout, _lg(rel), over))
+    assert wp.grad.dtype == F32 and ok, (fn, shape, dtype, over, rel)
+
+
+@pytest.mark.parametrize('shape,dtype', [((64, 64), F32), ((96, 96), BF16)], ids=lambda v: str(v).replace('torch.', ''))
+def test_convolution_function_at_64_offsets_launches_the_route(L, F, shape, dtype):
+    """k = 64 (tests/conv_lk_tables.py 't64'), beyond the row mask of the tile schedule: 64 -> 64 on fp32 rows runs the offset-chunk
+    kernel, 96 -> 96 under bf16 autocast keeps bf16 rows on the pair schedule -- forward and input gradient on the entry
+    _conv_route names, the results finite and of the types of the k <= 31 test"""
+    import conv_lk_tables as T
+    cin, cout = shape
+    nbr, n_in = T.make_table('t64')
+    k, n_out = nbr.shape
+    assert int(nbr.max()) < n_in and int(nbr.min()) >= -1
+    km = F.KernelMap(nbr.cuda(), T.invert(nbr, n_in).cuda(), n_in, n_out, False, None)
+    wp = R.make_weights(k, cin, cout, 'unit', seed=4).cuda().requires_grad_(True)
+    x = R.make_rows('unit', n_in, cin, dtype, 41).cuda().float().requires_grad_(True)
+    g = R.make_rows('unit', n_out, cout, dtype, 42).cuda().float()
+    with _Spy(L) as spy:
+        with torch.autocast('cuda', dtype=dtype, enabled=dtype != F32):
+            y = F.ConvolutionFunction.apply(x, wp, km, False)
+        _sync('ConvolutionFunction.forward k=64')
+        fwd, spy.names = spy.conv_entries(), []
+        y.backward(g.to(y.dtype))
+        _sync('ConvolutionFunction.backward k=64')
+        bwd = spy.conv_entries()
+    rf, rb = F._conv_route(dtype, cin, cout, k, n_out), F._conv_route(dtype, cout, cin, k, n_in)
+    assert fwd == [rf.entry] and bwd == [rb.entry], (fwd, bwd, rf, rb)
+    assert rf.entry == ('u2mkd_conv_forward_lk' if dtype == F32 else 'u2mkd_conv_forward_pairs_bf16')
+    assert y.dtype == dtype and x.grad.dtype == F32 and wp.grad.shape == (k, cin, cout)
+    assert bool(torch.isfinite(y).all()) and bool(torch.isfinite(x.grad).all()) and bool(torch.isfinite(wp.grad).all())

@@ -13,10 +13,11 @@ GPU only: CPU tensors raise (there is no fallback path).
 """
 from __future__ import annotations
 
+import functools
 import os
 import threading
-
 import weakref
+from typing import NamedTuple, Optional
 
 import torch
 from torch.autograd import Function
@@ -732,29 +733,20 @@ class TileSchedule:
         ``epilogue`` = (scale [cout], shift [cout], residual [n, cout] or None, relu): a folded eval-mode BatchNorm
         (conv_eval_affine); only where ``supports_epilogue`` says so."""
         n_in, cin = feats.shape
-        # fp32 rows: f16x2 (arith 4) where the tile kernel has it, else the library default (bf16x3 / f32)
-        ar = 4 if feats.dtype == torch.float32 and _tiles_arith(cin, cout, self.k) == 4 else 0
+        r = _tiles_route(feats.dtype, cin, cout, self.k, epilogue is not None)
+        if epilogue is not None and not r.epilogue:
+            raise RuntimeError(f'TileSchedule.run: no folded store for {cin} -> {cout} channels of {feats.dtype} rows ({r.entry})')
+        w = _weight_layout(weight, transpose, r.fragments, arith=r.arith)
+        if r.entry == 'u2mkd_conv_forward_sorted':
+            L.call(r.entry, L.ptr(feats), n_in, cin, L.ptr(w), cout, L.ptr(self.nbr_s),
+                   L.ptr(self.order), L.ptr(self.tile_order), self.n, self.k, int(kflip), L.ptr(out), L.stream())
+            return out
+        tail = () if feats.dtype != torch.float32 else (r.arith,)      # (the 16-bit entries have their arithmetic in their name)
         if epilogue is not None:
             sc, sh, res, relu = epilogue
-            wf = _weight_layout(weight, transpose, True, arith=ar)
-            L.call('u2mkd_conv_forward_tiles_ep', L.ptr(feats), n_in, cin, L.ptr(wf), cout, L.ptr(self.nbr_s),
-                   L.ptr(self.order), L.ptr(self.items), L.ptr(self.n_items), self.n, self.k, int(kflip), ar, L.ptr(sc), L.ptr(sh),
-                   L.ptr(res), int(relu), L.ptr(out), L.stream())
-            return out
-        if feats.dtype != torch.float32:         # bf16 / fp16 storage: rows in and out in that type, one weight plane of it
-            wf = _weight_layout(weight, transpose, True, arith=_arith16(feats.dtype))
-            L.call(_entry('u2mkd_conv_forward_tiles', feats.dtype), L.ptr(feats), n_in, cin, L.ptr(wf), cout, L.ptr(self.nbr_s),
-                   L.ptr(self.order), L.ptr(self.items), L.ptr(self.n_items), self.n, self.k, int(kflip), L.ptr(out),
-                   L.stream())
-        elif L.load().u2mkd_conv_tiles_supported(cin, cout, self.k):
-            wf = _weight_layout(weight, transpose, True, arith=ar)
-            L.call('u2mkd_conv_forward_tiles', L.ptr(feats), n_in, cin, L.ptr(wf), cout, L.ptr(self.nbr_s),
-                   L.ptr(self.order), L.ptr(self.items), L.ptr(self.n_items), self.n, self.k, int(kflip), ar, L.ptr(out),
-                   L.stream())
-        else:
-            wt = _weight_layout(weight, transpose, False)
-            L.call('u2mkd_conv_forward_sorted', L.ptr(feats), n_in, cin, L.ptr(wt), cout, L.ptr(self.nbr_s),
-                   L.ptr(self.order), L.ptr(self.tile_order), self.n, self.k, int(kflip), L.ptr(out), L.stream())
+            tail += (L.ptr(sc), L.ptr(sh), L.ptr(res), int(relu))
+        L.call(r.entry, L.ptr(feats), n_in, cin, L.ptr(w), cout, L.ptr(self.nbr_s), L.ptr(self.order), L.ptr(self.items),
+               L.ptr(self.n_items), self.n, self.k, int(kflip), *tail, L.ptr(out), L.stream())
         return out
 
 
@@ -839,21 +831,14 @@ class PairSchedule:
         if n_rows == 0:
             return out
         y = _scratch(self.cap * cout * 4, feats.device)
-        if feats.dtype != torch.float32:         # bf16 / fp16 storage (wt = the arith-3 / arith-5 fragments): scratch rows y in that type too
-            L.call(_entry('u2mkd_conv_forward_pairs', feats.dtype), L.ptr(feats), n, cin, L.ptr(wt), cout, L.ptr(idx), L.ptr(self.tile_k),
-                   L.ptr(self.meta), self.cap, self.k, L.ptr(y), st)
-            L.call(_entry('u2mkd_pairs_gather_sum', feats.dtype), L.ptr(y), L.ptr(pos), n_rows, self.k, cout, L.ptr(out), st)
-            return out
-        if fragments:
-            L.call('u2mkd_conv_forward_pairs_f16x2' if fragments == 2 else 'u2mkd_conv_forward_pairs_x3', L.ptr(feats), n, cin, L.ptr(wt), cout, L.ptr(idx), L.ptr(self.tile_k),
-                   L.ptr(self.meta), self.cap, self.k, L.ptr(y), st)
-        else:
-            L.call('u2mkd_conv_forward_pairs', L.ptr(feats), n, cin, L.ptr(wt), cout, L.ptr(idx), L.ptr(self.tile_k),
-                   L.ptr(self.meta), self.cap, self.k, variant, L.ptr(y), st)
+        r = _pairs_route(feats.dtype, fragments, epilogue is not None)
+        if epilogue is not None and not r.epilogue:
+            raise RuntimeError(f'PairSchedule.run: no folded store on {feats.dtype} rows ({r.gather})')
+        L.call(r.entry, L.ptr(feats), n, cin, L.ptr(wt), cout, L.ptr(idx), L.ptr(self.tile_k), L.ptr(self.meta), self.cap, self.k,
+               *((variant,) if r.entry == 'u2mkd_conv_forward_pairs' else ()), L.ptr(y), st)      # (the f32-MFMA kernel alone takes ``variant``)
         if epilogue is not None:      # folded eval-mode BatchNorm (+ residual, + ReLU) at the gather-sum's store
             sc, sh, res, relu = epilogue
-            L.call('u2mkd_pairs_gather_sum_ep', L.ptr(y), L.ptr(pos), n_rows, self.k, cout, L.ptr(sc), L.ptr(sh), L.ptr(res), int(relu),
-                   L.ptr(out), st)
+            L.call(r.gather, L.ptr(y), L.ptr(pos), n_rows, self.k, cout, L.ptr(sc), L.ptr(sh), L.ptr(res), int(relu), L.ptr(out), st)
             return out
         sink = BN_STATS_SINK[0]
         if sink is not None and sink.partial is None and out.dtype == torch.float32 and _stats_in_store(n_rows, cout):
@@ -863,7 +848,7 @@ class PairSchedule:
             L.call('u2mkd_pairs_gather_sum_stats', L.ptr(y), L.ptr(pos), n_rows, self.k, cout, L.ptr(out), L.ptr(partial), st)
             sink.partial, sink.slab_rows, sink.of = partial, rows, (out.data_ptr(), n_rows, cout)
             return out
-        L.call('u2mkd_pairs_gather_sum', L.ptr(y), L.ptr(pos), n_rows, self.k, cout, L.ptr(out), st)
+        L.call(r.gather, L.ptr(y), L.ptr(pos), n_rows, self.k, cout, L.ptr(out), st)
         return out
 
 
@@ -898,7 +883,6 @@ class KernelMap:
         self.symmetric = bool(symmetric)
         self.out_coords = out_coords
         self._rulebook = None
-        self._pairs = None
         self._pair_blocks = None
         self._sorted = {}
         self._pair_schedule = None
@@ -950,36 +934,15 @@ class KernelMap:
         if self.k > _WGRAD_BLOCK:
             raise RuntimeError(f'KernelMap.pairs_plan: kernel volume {self.k} above {_WGRAD_BLOCK}: the weight gradient takes its offsets in '
                                'blocks (KernelMap.pairs_blocks)')
-        if self._pairs is None:
-            self._note('pairs_plan')
-            k, n_out = self.k, self.n_out
-            dev = self.nbr.device
-            nblocks = max((n_out + 1023) // 1024, 1)
-            nbsizes = torch.zeros(k, dtype=torch.int32, device=dev)
-            block_counts = torch.empty(k, nblocks, dtype=torch.int32, device=dev)
-            cap = max(min(k * n_out, self.n_in * k), 1)
-            pairs = torch.empty(cap, 2, dtype=torch.int32, device=dev)
-            plan = torch.empty(L.load().u2mkd_wgrad_plan_ints(k), dtype=torch.int32, device=dev)
-            if n_out:
-                L.call('u2mkd_kmap_sizes', L.ptr(self.nbr), n_out, k, L.ptr(nbsizes), L.ptr(block_counts), L.stream())
-                L.call('u2mkd_kmap_compact', L.ptr(self.nbr), n_out, k, L.ptr(nbsizes), L.ptr(block_counts),
-                       L.ptr(pairs), L.stream())
-            L.call('u2mkd_wgrad_plan', L.ptr(nbsizes), k, n_out, L.ptr(plan), L.stream())
-            self._pairs = (pairs, nbsizes, plan)
-        return self._pairs
+        return self.pairs_blocks()[0][2:]
 
     def pairs_blocks(self):
         """[(b0, b1, pairs, nbsizes, plan)]: ``pairs_plan`` per block of at most 64 offsets -- u2mkd_wgrad_plan is one wave of 64
         lanes.  ``nbr`` is [K, n_out], so offsets b0 .. b1 are a contiguous slice of it and a block is the compacted rulebook and
         the work split of that slice; up to 64 offsets there is one block, ``pairs_plan`` itself.  No host synchronisation."""
-        if self._pair_blocks is not None:
-            return self._pair_blocks[0]
-        if self.k <= _WGRAD_BLOCK:
-            self._pair_blocks = ([(0, self.k) + self.pairs_plan()], self._pairs[1])
-        else:
+        if self._pair_blocks is None:
             self._note('pairs_plan')
-            n_out = self.n_out
-            dev = self.nbr.device
+            n_out, dev = self.n_out, self.nbr.device
             nblocks = max((n_out + 1023) // 1024, 1)
             lib, st = L.load(), L.stream()
             nbsizes_all = torch.zeros(self.k, dtype=torch.int32, device=dev)
@@ -1002,15 +965,10 @@ class KernelMap:
 
     def rulebook(self):
         """torchsparse's (nbmaps [P,2], nbsizes [K]); trimming to P is the only host sync."""
-        if self._rulebook is None:
-            if self.k > _WGRAD_BLOCK:       # the blocks' rulebooks one after the other: offsets ascending, as v1.4.0 lists them
-                blocks = self.pairs_blocks()
-                totals = torch.stack([b[4][0] for b in blocks]).tolist()
-                self._rulebook = (torch.cat([b[2][:t] for b, t in zip(blocks, totals)]), self._pair_blocks[1])
-                return self._rulebook
-            pairs, nbsizes, plan = self.pairs_plan()
-            total = int(plan[0].item())
-            self._rulebook = (pairs[:total], nbsizes)
+        if self._rulebook is None:          # the blocks' rulebooks one after the other: offsets ascending, as v1.4.0 lists them
+            blocks = self.pairs_blocks()
+            totals = torch.stack([b[4][0] for b in blocks]).tolist()
+            self._rulebook = (torch.cat([b[2][:t] for b, t in zip(blocks, totals)]), self._pair_blocks[1])
         return self._rulebook
 
     def __len__(self):
@@ -1098,22 +1056,17 @@ def _conv_os(feats, weight, transpose, cout, kmap, inverse, n_rows, kflip, epilo
     gradient of a symmetric (submanifold) map computed on the forward table with mirrored offsets -- in the
     pair schedule that is simply the swapped-role walk."""
     out = torch.empty(n_rows, cout, dtype=feats.dtype, device=feats.device)
-    if kmap.k > _PAIRS_MAX_K:                    # the pair schedule's scratch is K * n * cout * 4 bytes: every call on the offset-chunk kernel
-        return _conv_lk(feats, weight, transpose, cout, kmap, inverse, n_rows, kflip, out)
-    rows16 = feats.dtype != torch.float32        # (ConvolutionFunction hands fp32, bf16 or fp16 rows)
-    if rows16 and not L.load().u2mkd_conv_tiles_supported(feats.shape[1], cout, kmap.k):
-        # bf16 / fp16 storage, every shape the tile kernel has no instantiation for (_conv_rows16_ok: multiples of 32)
-        wt = _weight_layout(weight, transpose, True, arith=_arith16(feats.dtype))
-        return kmap.pair_schedule().run(feats, wt, cout, bool(inverse) or bool(kflip), out)
-    if not rows16 and _pairs_mode(feats.shape[1], cout, n_rows):
-        x3 = _PAIRS_X3 and bool(L.load().u2mkd_conv_pairs_x3_supported(feats.shape[1], cout))
-        f2 = x3 and _pairs_f16x2(feats.shape[1], cout)          # the same kernel in f16x2 arithmetic (arith-4 fragments)
-        wt = _weight_layout(weight, transpose, x3, arith=4 if f2 else 0)
-        return kmap.pair_schedule().run(feats, wt, cout, bool(inverse) or bool(kflip), out, fragments=2 if f2 else x3, epilogue=epilogue)
-    if kmap.k > _TILES_MAX_K:                 # no row mask, no tile schedule beyond 31 offsets
-        return _conv_lk(feats, weight, transpose, cout, kmap, inverse, n_rows, kflip, out)
+    r = _conv_route(feats.dtype, feats.shape[1], cout, kmap.k, n_rows, epilogue is not None)
+    if epilogue is not None and not r.epilogue:
+        raise RuntimeError(f'conv3d: no folded store on {r.entry} ({feats.shape[1]} -> {cout} channels, kernel volume {kmap.k})')
+    if r.schedule == 'pairs':
+        wt = _weight_layout(weight, transpose, r.fragments, arith=r.arith)
+        return kmap.pair_schedule().run(feats, wt, cout, bool(inverse) or bool(kflip), out, fragments=2 if r.arith == 4 else r.fragments,
+                                        epilogue=epilogue)
     if inverse and kmap.nbr_inv is None:      # symmetric map: the inverse table is the mirrored forward table
         inverse, kflip = False, 1 - int(kflip)
+    if r.schedule == 'lk':
+        return _conv_lk(feats, weight, transpose, cout, kmap.nbr_inv if inverse else kmap.nbr, n_rows, kflip, out)
     sch = kmap.schedule(inverse)
     assert sch.n == n_rows
     return sch.run(feats, weight, transpose, cout, kflip, out, epilogue=epilogue)
@@ -1124,74 +1077,139 @@ _PAIRS_MAX_K = 64        # beyond: every forward / input gradient on the offset-
 _LK_MAX_K = 343          # u2mkd_conv_lk_supported: 7 x 7 x 7
 
 
-def _lk_route(cin, cout, k, n_rows, rows16=False):
-    """True where _conv_os sends an fp32-row launch to the offset-chunk kernel (csrc/conv_lk.hip)"""
-    return k > _PAIRS_MAX_K or (k > _TILES_MAX_K and not rows16 and not _pairs_mode(cin, cout, n_rows))
+class Route(NamedTuple):
+    """What one launch of the conv / linear host path runs on (_conv_route, _dense_route)"""
+    schedule: str            # 'lk' (offset-chunk kernel) | 'pairs' | 'tiles' | 'dense' (nn.Linear, the 1 x 1 x 1 conv)
+    entry: str               # the C entry of the product
+    gather: Optional[str]    # pair schedule: the gather-sum entry that follows it
+    arith: int               # u2mkd_weight_fragments' arith code of the weights the entry reads
+    fragments: bool          # the weights in MFMA-fragment order (else row-major, the reduction contiguous)
+    epilogue: bool           # the folded eval-BatchNorm store (conv_eval_affine) exists on this route
 
 
-def _conv_lk(feats, weight, transpose, cout, kmap, inverse, n_rows, kflip, out):
-    """_conv_os on u2mkd_conv_forward_lk: the (inverse) table in natural row order, the offsets in chunks of 32; a symmetric map's
-    inverse roles on the forward table with mirrored offsets.  fp32 rows; the weights row-major as TileSchedule.run's
-    non-fragment path passes them."""
+# C entry -> (u2mkd_weight_fragments arith codes of the weights it reads, fragment order).  The fp32-row tile entries take the code
+# as an argument (4 where u2mkd_conv_tiles_arith says f16x2); every other entry has ONE.  _WFRAG_SLOT: _weight_layout's cache slot.
+_ENTRY_WEIGHTS = {
+    'u2mkd_conv_forward_lk': ((0,), False), 'u2mkd_conv_forward_sorted': ((0,), False),           # row-major fp32
+    'u2mkd_conv_forward_pairs': ((0,), False), 'u2mkd_linear_forward': ((0,), False),
+    'u2mkd_conv_forward_pairs_x3': ((0,), True), 'u2mkd_linear_forward_x3': ((0,), True),         # 0: the library's (bf16x3 / f32)
+    'u2mkd_conv_forward_pairs_f16x2': ((4,), True), 'u2mkd_linear_forward_f16x2': ((4,), True),   # 4: f16x2
+    'u2mkd_conv_forward_tiles': ((0, 4), True), 'u2mkd_conv_forward_tiles_ep': ((0, 4), True),
+    'u2mkd_conv_forward_tiles_bf16': ((3,), True), 'u2mkd_conv_forward_pairs_bf16': ((3,), True), 'u2mkd_linear_forward_bf16': ((3,), True),
+    'u2mkd_conv_forward_tiles_f16': ((5,), True), 'u2mkd_conv_forward_pairs_f16': ((5,), True), 'u2mkd_linear_forward_f16': ((5,), True)}
+_WFRAG_SLOT = {0: '_u2mkd_wfrag', 3: '_u2mkd_wfrag3', 4: '_u2mkd_wfrag4', 5: '_u2mkd_wfrag5'}
+
+
+def _route(schedule, entry, arith=None, gather=None, epilogue=False):
+    codes, fragments = _ENTRY_WEIGHTS[entry]
+    assert arith in codes if arith is not None else len(codes) == 1, (entry, arith)
+    return Route(schedule, entry, gather, codes[0] if arith is None else arith, fragments, epilogue)
+
+
+@functools.lru_cache(maxsize=None)
+def _tiles_route(rows, cin, cout, k, epilogue=False):
+    """TileSchedule.run's entry: 16-bit rows on their one-plane tile kernel; fp32 rows on the tile-pair kernel where it has the
+    shape (its folded-store form when ``epilogue``), every other shape on the sorted offset walkers."""
+    if rows != torch.float32:
+        return _route('tiles', _entry('u2mkd_conv_forward_tiles', rows))
+    if not L.load().u2mkd_conv_tiles_supported(cin, cout, k):
+        return _route('tiles', 'u2mkd_conv_forward_sorted')
+    return _route('tiles', 'u2mkd_conv_forward_tiles_ep' if epilogue else 'u2mkd_conv_forward_tiles',
+                  arith=4 if _tiles_arith(cin, cout, k) == 4 else 0, epilogue=True)
+
+
+@functools.lru_cache(maxsize=None)
+def _pairs_route(rows, fragments, epilogue=False):
+    """PairSchedule.run's two entries; ``fragments`` = 2: f16x2, True: bf16x3, False: the f32-MFMA pair kernel (16-bit rows: ignored)"""
+    if rows != torch.float32:
+        return _route('pairs', _entry('u2mkd_conv_forward_pairs', rows), gather=_entry('u2mkd_pairs_gather_sum', rows))
+    entry = 'u2mkd_conv_forward_pairs' + ('_f16x2' if fragments == 2 else '_x3' if fragments else '')
+    return _route('pairs', entry, gather='u2mkd_pairs_gather_sum_ep' if epilogue else 'u2mkd_pairs_gather_sum', epilogue=True)
+
+
+@functools.lru_cache(maxsize=None)
+def _route_of(rows, cin, cout, k, pairs, epilogue):
+    if k > _PAIRS_MAX_K:                      # the pair schedule's scratch is K * n * cout * 4 bytes: every call on the offset-chunk kernel
+        return _route('lk', 'u2mkd_conv_forward_lk')
+    if rows != torch.float32:                 # 16-bit storage: every shape the tile kernel has no instantiation for on the pair schedule
+        if not L.load().u2mkd_conv_tiles_supported(cin, cout, k):
+            return _pairs_route(rows, True)
+    elif pairs:
+        x3 = _PAIRS_X3 and bool(L.load().u2mkd_conv_pairs_x3_supported(cin, cout))
+        f2 = x3 and _pairs_f16x2(cin, cout)          # the same kernel in f16x2 arithmetic (arith-4 fragments)
+        return _pairs_route(rows, 2 if f2 else x3, epilogue)
+    if k > _TILES_MAX_K:                      # no row mask, no tile schedule beyond 31 offsets
+        return _route('lk', 'u2mkd_conv_forward_lk')
+    return _tiles_route(rows, cin, cout, k, epilogue)
+
+
+def _conv_route(rows, cin, cout, k, n_rows, epilogue=False):
+    """THE dispatch of a sparse conv launch (forward, transposed conv or input gradient) of cin -> cout channels on ``rows``
+    (float32 / bfloat16 / float16) over k offsets and ``n_rows`` destination rows: _conv_os launches what it says,
+    conv_epilogue_supported and _rows16_servable ask it, TileSchedule.run / PairSchedule.run name their entries through the same
+    _tiles_route / _pairs_route.  ``epilogue``: the folded store is wanted; ``.epilogue``: the route has one.  Cached per shape;
+    the switches read per call stay outside: _pairs_mode's and, where the folded store is asked for, conv_arith_is_default's."""
+    r = _route_of(rows, cin, cout, k, rows == torch.float32 and _pairs_mode(cin, cout, n_rows), bool(epilogue))
+    return r._replace(epilogue=False) if epilogue and r.epilogue and r.schedule == 'tiles' and not conv_arith_is_default() else r
+
+
+@functools.lru_cache(maxsize=None)
+def _rows16_servable(rows, cin, cout, k):
+    """A conv layer keeps 16-bit ``rows``: channel counts the 16-bit kernels take, and BOTH its launches -- (cin, cout) over the
+    outputs, (cout, cin) over the inputs -- off the offset-chunk kernel, which takes fp32 rows only.  Up to 31 offsets: always;
+    32 .. 64: where the pair schedule runs both; above 64 the layer computes on fp32 rows and rounds once."""
+    return _conv_rows16_ok(cin, cout) and 'lk' not in (_conv_route(rows, cin, cout, k, 0).schedule, _conv_route(rows, cout, cin, k, 0).schedule)
+
+
+def _conv_lk(feats, weight, transpose, cout, tbl, n_rows, kflip, out):
+    """_conv_os on u2mkd_conv_forward_lk: the (inverse) table ``tbl`` in natural row order, the offsets in chunks of 32.  fp32
+    rows; the weights row-major as TileSchedule.run passes them to the sorted walkers."""
     if feats.dtype != torch.float32:
-        raise RuntimeError(f'conv3d: kernel volume {kmap.k} on {feats.dtype} rows: the offset-chunk kernel takes fp32 rows')
-    if inverse and kmap.nbr_inv is None:
-        inverse, kflip = False, 1 - int(kflip)
-    tbl = kmap.nbr_inv if inverse else kmap.nbr
+        raise RuntimeError(f'conv3d: kernel volume {tbl.shape[0]} on {feats.dtype} rows: the offset-chunk kernel takes fp32 rows')
     assert tbl.shape[1] == n_rows
     n_in, cin = feats.shape
     wt = _weight_layout(weight, transpose, False)
-    L.call('u2mkd_conv_forward_lk', L.ptr(feats), n_in, cin, L.ptr(wt), cout, L.ptr(tbl), n_rows, n_rows, kmap.k, int(kflip),
+    L.call('u2mkd_conv_forward_lk', L.ptr(feats), n_in, cin, L.ptr(wt), cout, L.ptr(tbl), n_rows, n_rows, tbl.shape[0], int(kflip),
            L.ptr(out), L.stream())
     return out
 
 
-def _rows16_volume_ok(cin, cout, k):
-    """16-bit rows at kernel volume k: every volume the tile schedule takes; 32 .. 64 offsets where the pair schedule runs the
-    layer (the tile kernel's shapes would need the row mask); above 64 the layer computes on fp32 rows and rounds once."""
-    if k <= _TILES_MAX_K:
-        return True
-    return k <= _PAIRS_MAX_K and not L.load().u2mkd_conv_tiles_supported(cin, cout, k)
-
-
 def conv_epilogue_supported(feats, cin, cout, k, n_rows):
-    """True where conv_eval_affine can fold the affine into the convolution's store: fp32 rows on the tile-pair kernel
-    (u2mkd_conv_forward_tiles_ep) or on the pair schedule (u2mkd_pairs_gather_sum_ep)."""
-    if feats.dtype != torch.float32 or row_dtype() is not None or cin % 4 or cout % 4:
-        return False
-    if _lk_route(cin, cout, k, n_rows):           # the offset-chunk kernel has no folded store: conv, then BatchNorm
-        return False
-    if _pairs_mode(cin, cout, n_rows):
-        return True
-    return bool(L.load().u2mkd_conv_tiles_supported(cin, cout, k)) and conv_arith_is_default()
+    """True where conv_eval_affine can fold the affine into the convolution's store: fp32 rows on a route that has one (the
+    tile-pair kernel: u2mkd_conv_forward_tiles_ep; the pair schedule: u2mkd_pairs_gather_sum_ep; not the offset-chunk kernel)."""
+    takes = feats.dtype == torch.float32 and row_dtype() is None and cin % 4 == 0 and cout % 4 == 0
+    return takes and _conv_route(torch.float32, cin, cout, k, n_rows, epilogue=True).epilogue
 
 
-_TILES_ARITH = {}
-_PAIRS_F16X2 = {}
-
-
+@functools.lru_cache(maxsize=None)
 def _pairs_f16x2(cin, cout):
     """u2mkd_conv_pairs_f16x2_supported, cached: the pair-schedule / dense kernels run this shape in f16x2 arithmetic."""
-    key = (cin, cout)
-    hit = _PAIRS_F16X2.get(key)
-    if hit is None:
-        hit = _PAIRS_F16X2[key] = bool(L.load().u2mkd_conv_pairs_f16x2_supported(cin, cout))
-    return hit
+    return bool(L.load().u2mkd_conv_pairs_f16x2_supported(cin, cout))
 
 
-
+@functools.lru_cache(maxsize=None)
 def _tiles_arith(cin, cout, k):
     """u2mkd_conv_tiles_arith, cached: the arithmetic code the tile kernel runs a layer of fp32 rows in (4 = f16x2, 2 = bf16x3,
     1 = f32, 0 = not a tile-kernel layer)."""
-    key = (cin, cout, k)
-    hit = _TILES_ARITH.get(key)
-    if hit is None:
-        hit = _TILES_ARITH[key] = int(L.load().u2mkd_conv_tiles_arith(cin, cout, k))
-    return hit
+    return int(L.load().u2mkd_conv_tiles_arith(cin, cout, k))
 
 
 def conv_arith_is_default():
     return os.environ.get('U2MKD_CONV_SCHEDULE') in (None, 'tiles', 'pairs')
+
+
+def _conv_geometry(input, kernel_size, stride, dilation, transposed):
+    """(kernel map, coordinates, tensor stride of the output) of a conv over ``input``: the map of the key, built at its first use;
+    a transposed conv runs on the map its downsampling conv left behind"""
+    if transposed:
+        out_stride = tuple(input.stride[i] // stride[i] for i in range(3))
+        return input.kmaps[(out_stride, kernel_size, stride, dilation)], input.cmaps[out_stride], out_stride
+    key = (input.stride, kernel_size, stride, dilation)
+    kmap = input.kmaps.get(key)
+    if kmap is None:
+        # v1.4.0 builds the offsets from the tensor stride only (dilation is not applied)
+        kmap = input.kmaps[key] = build_kmap(input.coords, input.stride, kernel_size, stride)
+    return kmap, kmap.out_coords, tuple(input.stride[i] * stride[i] for i in range(3))
 
 
 def conv_eval_affine(input: SparseTensor, conv, scale, shift, relu, residual=None):
@@ -1206,19 +1224,8 @@ def conv_eval_affine(input: SparseTensor, conv, scale, shift, relu, residual=Non
         return None
     feats = input.feats
     k, cin, cout = weight.shape
-    if not conv.transposed:
-        key = (input.stride, kernel_size, stride, dilation)
-        kmap = input.kmaps.get(key)
-        if kmap is None:
-            kmap = build_kmap(input.coords, input.stride, kernel_size, stride)
-            input.kmaps[key] = kmap
-        inverse, n_rows = False, kmap.n_out
-        out_coords, out_stride = kmap.out_coords, tuple(input.stride[i] * stride[i] for i in range(3))
-    else:
-        out_stride = tuple(input.stride[i] // stride[i] for i in range(3))
-        kmap = input.kmaps[(out_stride, kernel_size, stride, dilation)]
-        inverse, n_rows = True, kmap.n_in
-        out_coords = input.cmaps[out_stride]
+    kmap, out_coords, out_stride = _conv_geometry(input, kernel_size, stride, dilation, conv.transposed)
+    inverse, n_rows = (True, kmap.n_in) if conv.transposed else (False, kmap.n_out)
     if not conv_epilogue_supported(feats, cin, cout, k, n_rows) or feats.shape[1] != cin:
         return None
     res = None
@@ -1356,9 +1363,7 @@ def _weight_layout(weight, transpose, fragments, arith=0):
             and weight.is_contiguous() and base.requires_grad == weight.requires_grad:
         holder, tag = base, ':%dx%dx%d' % (k, r, c)
     if fragments:
-        # arith 0 = the library's fp32-row arithmetic (bf16x3 / f32), 3 = ONE bf16 plane (bf16 storage), 4 = f16x2 (tile kernel),
-        # 5 = ONE fp16 plane (fp16 storage); a slot per arith: a module used under bf16 and then fp16 autocast keeps both images
-        slot = {3: '_u2mkd_wfrag3', 4: '_u2mkd_wfrag4', 5: '_u2mkd_wfrag5'}.get(arith, '_u2mkd_wfrag') + tag
+        slot = _WFRAG_SLOT.get(arith, _WFRAG_SLOT[0]) + tag           # (a slot per arith code: _ENTRY_WEIGHTS)
         hit = holder.__dict__.get(slot)
         if hit is None or hit[0] != stamp:
             nbytes = L.load().u2mkd_weight_fragments_bytes(k, r, c, arith)
@@ -1415,8 +1420,21 @@ def _identity_pairs(n, device):
 _LINEAR_X3 = os.environ.get('U2MKD_LINEAR_X3', '1') != '0'
 
 
-def _dense_x3_ok(cin, cout):
-    return _PAIRS_X3 and _LINEAR_X3 and bool(L.load().u2mkd_conv_pairs_x3_supported(cin, cout))
+@functools.lru_cache(maxsize=None)
+def _dense_fragment_route(rows, cin, cout):
+    """_dense_x3's entry: 16-bit rows on their one plane, fp32 rows in f16x2 arithmetic where the kernel has it, else bf16x3"""
+    if rows != torch.float32:
+        return _route('dense', _entry('u2mkd_linear_forward', rows))
+    return _route('dense', 'u2mkd_linear_forward_f16x2' if _pairs_f16x2(cin, cout) else 'u2mkd_linear_forward_x3')
+
+
+@functools.lru_cache(maxsize=None)
+def _dense_route(rows, cin, cout):
+    """_conv_route's counterpart for x @ W (LinearFunction, PointwiseConvFunction, conv3d's 1 x 1 x 1 branch): _dense_x3 on 16-bit
+    rows and where the bf16x3 pair kernel has the shape (U2MKD_PAIRS_X3 / U2MKD_LINEAR_X3 = 0: nowhere on fp32 rows), else _dense."""
+    if rows != torch.float32 or (_PAIRS_X3 and _LINEAR_X3 and bool(L.load().u2mkd_conv_pairs_x3_supported(cin, cout))):
+        return _dense_fragment_route(rows, cin, cout)
+    return _route('dense', 'u2mkd_linear_forward')
 
 
 def _dense_x3(x, weight, forward, bias=None, kernel_layout=False):
@@ -1430,12 +1448,10 @@ def _dense_x3(x, weight, forward, bias=None, kernel_layout=False):
         cout = weight.shape[-1] if forward else weight.shape[-2]
     else:
         cout = weight.shape[0] if forward else weight.shape[1]
-    rows16 = x.dtype != torch.float32
-    f2 = not rows16 and _pairs_f16x2(x.shape[1], cout)
-    wf = _weight_layout(weight, forward if kernel_layout else not forward, True, arith=_arith16(x.dtype) if rows16 else (4 if f2 else 0))
+    r = _dense_fragment_route(x.dtype, x.shape[1], cout)
+    wf = _weight_layout(weight, forward if kernel_layout else not forward, True, arith=r.arith)
     y = torch.empty(n, cout, dtype=x.dtype, device=x.device)
-    L.call(_entry('u2mkd_linear_forward', x.dtype) if rows16 else ('u2mkd_linear_forward_f16x2' if f2 else 'u2mkd_linear_forward_x3'), L.ptr(x), n,
-           x.shape[1], L.ptr(wf), cout, L.ptr(bias), L.ptr(y), L.stream())
+    L.call(r.entry, L.ptr(x), n, x.shape[1], L.ptr(wf), cout, L.ptr(bias), L.ptr(y), L.stream())
     return y
 
 
@@ -1467,6 +1483,38 @@ def _leaf_behind_view(w):
     return base
 
 
+def _enter_rows(ctx, x, cin, cout, k=None):
+    """A conv / linear forward's way in: (x as contiguous rows of the type the layer computes on, the type _exit_rows rounds its
+    result to or None).  16-bit storage (autocast to bfloat16 or float16): rows of that type in and out, as torchsparse's
+    custom_fwd(cast_inputs=half); a layer without a 16-bit kernel (the 4-channel stem; a conv of ``k`` offsets: _rows16_servable)
+    computes on fp32 rows and rounds the result once.  ctx.in_dtype: what the backward casts the input gradient back to."""
+    want16 = row_dtype()
+    rows16 = want16 if want16 is not None and (_conv_rows16_ok(cin, cout) if k is None else _rows16_servable(want16, cin, cout, k)) else None
+    ctx.in_dtype = x.dtype
+    return _rows(x, rows16), (want16 if rows16 is None else None)
+
+
+def _exit_rows(y, round_to):
+    return y if round_to is None else y.to(round_to)
+
+
+def _wgrad_launch(ctx, a, ca, b, cb, blocks, n_rows, swap, weight, owner, overlap_inline):
+    """The weight gradient of every backward: gw like ``weight``, per offset of each block of ``blocks`` (KernelMap.pairs_blocks;
+    a linear layer: the one block of _identity_pairs) the sum over its pairs of a[first]^T b[second] (``swap``: sides exchanged),
+    one launch per block on the stream _wgrad_side grants, sharing a workspace sized for the widest.  -> (gw, side, deferred,
+    the workspace: the caller holds it until it has joined ``side`` -- freed earlier, the allocator hands it to the input gradient)"""
+    nbytes = L.load().u2mkd_conv_wgrad_pairs_workspace_bytes(n_rows, ca, cb, max(b1 - b0 for b0, b1, *_ in blocks))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=a.device)
+    gw = torch.empty_like(weight)
+    side, deferred_join = _wgrad_side(owner, ctx.weight_is_param, a.device, overlap_inline, a, b, ws, gw,
+                                       *(t for blk in blocks for t in (blk[2], blk[4])), allow=getattr(ctx, 'overlap_ok', True))
+    st = side.cuda_stream if side is not None else L.stream()
+    for b0, b1, pairs, _, plan in blocks:
+        L.call(_entry('u2mkd_conv_wgrad_pairs', a.dtype), L.ptr(a), ca, L.ptr(b), cb, L.ptr(pairs), L.ptr(plan), n_rows, b1 - b0, swap,
+               L.ptr(ws), nbytes, L.ptr(gw if len(blocks) == 1 else gw[b0:b1]), st)
+    return gw, side, deferred_join, ws
+
+
 class LinearFunction(Function):
     """y = x @ weight.T + bias (nn.Linear semantics) on the conv pipeline: forward and input
     gradient on the pair kernel's dense mode, weight gradient on the pair-list wgrad kernel."""
@@ -1485,10 +1533,7 @@ class LinearFunction(Function):
         # the bias IS a leaf parameter (not a padded / cast copy): its gradient, too, is read by nobody before the backward ends
         ctx.bias_param = bias if (bias is not None and bias.is_leaf and bias.requires_grad and bias.dtype == torch.float32) else None
         ctx.overlap_ok = _deferred_overlap_ok()
-        want16 = row_dtype()
-        rows16 = want16 if _conv_rows16_ok(weight.shape[1], weight.shape[0]) else None
-        ctx.in_dtype = x.dtype
-        x = _rows(x, rows16)
+        x, round_to = _enter_rows(ctx, x, weight.shape[1], weight.shape[0])
         if x.dim() != 2 or x.shape[1] != weight.shape[1]:
             raise RuntimeError(f'linear: input {tuple(x.shape)} does not match weight {tuple(weight.shape)}')
         if weight.shape[1] % 4 != 0 or weight.shape[0] % 4 != 0:
@@ -1499,9 +1544,9 @@ class LinearFunction(Function):
         if x.shape[0] == 0:
             return x.new_zeros(0, weight.shape[0])
         b = bias.contiguous().float() if bias is not None else None
-        ctx.x3 = rows16 is not None or _dense_x3_ok(weight.shape[1], weight.shape[0])
-        y = _dense_x3(x, weight, True, b) if ctx.x3 else _dense(x, weight, b)
-        return y.to(want16) if (want16 is not None and rows16 is None) else y
+        ctx.fragments = _dense_route(x.dtype, weight.shape[1], weight.shape[0]).fragments      # (the input gradient takes the same route)
+        y = _dense_x3(x, weight, True, b) if ctx.fragments else _dense(x, weight, b)
+        return _exit_rows(y, round_to)
 
     @staticmethod
     def backward(ctx, g):
@@ -1516,15 +1561,9 @@ class LinearFunction(Function):
         # (the weight gradient first: it goes to the side stream and runs next to gx)
         if ctx.needs_input_grad[1]:
             pairs, plan = _identity_pairs(n, g.device)
-            lib = L.load()
-            nbytes = lib.u2mkd_conv_wgrad_pairs_workspace_bytes(n, cout, cin, 1)
-            ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=g.device)
-            gw = torch.empty_like(weight)
-            side, deferred_join = _wgrad_side(ctx.weight_owner if ctx.weight_is_param else weight, ctx.weight_is_param, g.device,
-                                               ctx.needs_input_grad[0], x, g, ws, gw, pairs, plan, allow=getattr(ctx, 'overlap_ok', True))
-            L.call(_entry('u2mkd_conv_wgrad_pairs', x.dtype), L.ptr(g), cout, L.ptr(x), cin,
-                   L.ptr(pairs), L.ptr(plan), n, 1, 0, L.ptr(ws), nbytes, L.ptr(gw), side.cuda_stream if side is not None else L.stream())
-        if ctx.needs_input_grad[0] and ctx.x3:
+            gw, side, deferred_join, ws = _wgrad_launch(ctx, g, cout, x, cin, [(0, 1, pairs, None, plan)], n, 0, weight,       # dW = dY^T X
+                                                    ctx.weight_owner if ctx.weight_is_param else weight, ctx.needs_input_grad[0])
+        if ctx.needs_input_grad[0] and ctx.fragments:
             gx = _dense_x3(g, weight, False)
         elif ctx.needs_input_grad[0]:
             w_t = torch.empty(1, cin, cout, dtype=torch.float32, device=g.device)     # [cin][cout] = W^T rows
@@ -1568,10 +1607,7 @@ class PointwiseConvFunction(Function):
         ctx.weight_is_param = kernel.is_leaf
         ctx.overlap_ok = _deferred_overlap_ok()
         cin, cout = kernel.shape[-2], kernel.shape[-1]
-        want16 = row_dtype()
-        rows16 = want16 if _conv_rows16_ok(cin, cout) else None
-        ctx.in_dtype = x.dtype
-        x = _rows(x, rows16)
+        x, round_to = _enter_rows(ctx, x, cin, cout)
         if x.dim() != 2 or x.shape[1] != cin:
             raise RuntimeError(f'conv3d (1x1x1): input {tuple(x.shape)} does not match kernel {tuple(kernel.shape)}')
         ctx.save_for_backward(x, kernel)
@@ -1579,8 +1615,7 @@ class PointwiseConvFunction(Function):
         if x.shape[0] == 0:
             return x.new_zeros(0, cout)
         b = bias.contiguous().float() if bias is not None else None
-        y = _dense_x3(x, kernel, True, b, kernel_layout=True)
-        return y.to(want16) if (want16 is not None and rows16 is None) else y
+        return _exit_rows(_dense_x3(x, kernel, True, b, kernel_layout=True), round_to)
 
     @staticmethod
     def backward(ctx, g):
@@ -1594,13 +1629,8 @@ class PointwiseConvFunction(Function):
         side, deferred_join = None, False
         if ctx.needs_input_grad[1]:
             pairs, plan = _identity_pairs(n, g.device)
-            nbytes = L.load().u2mkd_conv_wgrad_pairs_workspace_bytes(n, cin, cout, 1)
-            ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=g.device)
-            gw = torch.empty_like(kernel)
-            side, deferred_join = _wgrad_side(kernel, ctx.weight_is_param, g.device, ctx.needs_input_grad[0], x, g, ws, gw, pairs, plan,
-                                               allow=getattr(ctx, 'overlap_ok', True))
-            L.call(_entry('u2mkd_conv_wgrad_pairs', x.dtype), L.ptr(x), cin, L.ptr(g), cout,
-                   L.ptr(pairs), L.ptr(plan), n, 1, 0, L.ptr(ws), nbytes, L.ptr(gw), side.cuda_stream if side is not None else L.stream())
+            gw, side, deferred_join, ws = _wgrad_launch(ctx, x, cin, g, cout, [(0, 1, pairs, None, plan)], n, 0, kernel, kernel,
+                                                    ctx.needs_input_grad[0])
         if ctx.needs_input_grad[0]:
             gx = _dense_x3(g, kernel, False, kernel_layout=True)
         if side is not None and not deferred_join:
@@ -1690,13 +1720,7 @@ class ConvolutionFunction(Function):
         ctx.weight_is_param = param.is_leaf and weight.data_ptr() == param.data_ptr() and weight.dtype == param.dtype
         ctx.overlap_ok = _deferred_overlap_ok()
         k, cin, cout = weight.shape
-        # 16-bit storage (autocast to bfloat16 or float16): rows of that type in and out, as torchsparse's
-        # custom_fwd(cast_inputs=half); shapes without a 16-bit kernel (the 4-channel stem) compute on fp32 rows and round the
-        # result once
-        want16 = row_dtype()
-        rows16 = want16 if _conv_rows16_ok(cin, cout) and _rows16_volume_ok(cin, cout, k) else None
-        ctx.in_dtype = input.dtype
-        input = _rows(input, rows16)
+        input, round_to = _enter_rows(ctx, input, cin, cout, k)
         if input.shape[1] != cin:
             raise RuntimeError(f'conv3d: input has {input.shape[1]} channels, kernel expects {cin}')
         if cin % 4 != 0:
@@ -1713,7 +1737,7 @@ class ConvolutionFunction(Function):
         ctx.save_for_backward(input, weight)
         ctx.kmap = kmap
         ctx.transposed = transposed
-        return out.to(want16) if (want16 is not None and rows16 is None) else out
+        return _exit_rows(out, round_to)
 
     @staticmethod
     def backward(ctx, grad_output):
@@ -1725,32 +1749,16 @@ class ConvolutionFunction(Function):
         # The two gradients are independent: the weight gradient runs on a side stream next to
         # the input gradient (each is a short grid with a long tail; together they fill the
         # chip) and is joined before this function returns, so autograd sees ordinary tensors.
-        do_w = ctx.needs_input_grad[1]
-        do_x = ctx.needs_input_grad[0]
+        do_x, do_w = ctx.needs_input_grad[:2]
         side, deferred_join = None, False
         if do_w:
             # dW[k] = sum over the offset's pairs of X[in]^T dY[out] (transposed conv: roles swapped)
-            # (above 64 offsets: one launch per block of 64, each into its slice grad_weight[b0:b1]; the launches follow each
-            # other on one stream and share the workspace)
-            blocks = kmap.pairs_blocks()
-            lib = L.load()
-            nbytes = lib.u2mkd_conv_wgrad_pairs_workspace_bytes(kmap.n_out, cin, cout, min(k, _WGRAD_BLOCK))      # (the widest block)
-            ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=g.device)
-            grad_weight = torch.empty_like(weight)
-            used = (blocks[0][2], blocks[0][4]) if len(blocks) == 1 else [t for b in blocks for t in (b[2], b[4])]
-            side, deferred_join = _wgrad_side(weight, ctx.weight_is_param, g.device, do_x, input, g, ws, grad_weight, *used,
-                                               allow=getattr(ctx, 'overlap_ok', True))
-            st = side.cuda_stream if side is not None else L.stream()
-            for b0, b1, pairs, _, plan in blocks:
-                L.call(_entry('u2mkd_conv_wgrad_pairs', input.dtype), L.ptr(input), cin, L.ptr(g), cout, L.ptr(pairs), L.ptr(plan),
-                       kmap.n_out, b1 - b0, 1 if transposed else 0, L.ptr(ws), nbytes, L.ptr(grad_weight[b0:b1]), st)
+            grad_weight, side, deferred_join, ws = _wgrad_launch(ctx, input, cin, g, cout, kmap.pairs_blocks(), kmap.n_out,
+                                                             1 if transposed else 0, weight, weight, do_x)
         if do_x:
             # dX[i] = sum_k dY[out_k(i)] @ W[k]^T : same kernel on the swapped-role table,
             # B_k = W[k] read as [cin][cout] (reduction over cout contiguous).
-            if not transposed:
-                inverse, kflip = (False, 1) if kmap.symmetric else (True, 0)
-            else:
-                inverse, kflip = False, 0
+            inverse, kflip = (False, 0) if transposed else ((False, 1) if kmap.symmetric else (True, 0))
             if cout % 4 != 0:
                 raise RuntimeError(f'conv3d backward: out_channels={cout} must be a multiple of 4')
             grad_input = _conv_os(g, weight, False, cin, kmap, inverse, input.shape[0], kflip)
@@ -1787,7 +1795,7 @@ def conv3d(input: SparseTensor, weight: torch.Tensor, kernel_size, bias=None, st
     if kernel_size == (1, 1, 1) and stride == (1, 1, 1) and dilation == (1, 1, 1):
         w = weight[0] if weight.dim() == 3 else weight          # kernel [1, cin, cout] or [cin, cout]
         if (weight.dim() == 2 or weight.shape[0] == 1) and weight.is_contiguous() and weight.dtype == torch.float32 \
-                and _dense_x3_ok(w.shape[0], w.shape[1]) and feats.is_cuda and feats.dim() == 2 and feats.shape[1] == w.shape[0]:
+                and _dense_route(torch.float32, w.shape[0], w.shape[1]).fragments and feats.is_cuda and feats.dim() == 2 and feats.shape[1] == w.shape[0]:
             # the kernel in its own [1, cin, cout] layout: cached fragments, no transposed copy (PointwiseConvFunction)
             feats = PointwiseConvFunction.apply(feats, weight, bias)
         elif w.shape[0] % 4 == 0 and w.shape[1] % 4 == 0:
@@ -1800,25 +1808,12 @@ def conv3d(input: SparseTensor, weight: torch.Tensor, kernel_size, bias=None, st
     elif kernel_size[0] * kernel_size[1] * kernel_size[2] > _LK_MAX_K:
         raise ValueError('conv3d: kernel volume %d (kernel_size %s) above %d' % (kernel_size[0] * kernel_size[1] * kernel_size[2],
                                                                                    kernel_size, _LK_MAX_K))
-    elif not transposed:
-        key = (input.stride, kernel_size, stride, dilation)
-        kmap = input.kmaps.get(key)
-        if kmap is None:
-            # v1.4.0 builds the offsets from the tensor stride only (dilation is not applied)
-            kmap = build_kmap(coords, input.stride, kernel_size, stride)
-            input.kmaps[key] = kmap
-        feats = _conv_any_channels(feats, weight, kmap, transposed)
-        if bias is not None:
-            feats = feats + bias
-        output = SparseTensor(coords=kmap.out_coords, feats=feats,
-                              stride=tuple(input.stride[k] * stride[k] for k in range(3)))
     else:
-        tensor_stride = tuple(input.stride[k] // stride[k] for k in range(3))
-        kmap = input.kmaps[(tensor_stride, kernel_size, stride, dilation)]
+        kmap, out_coords, out_stride = _conv_geometry(input, kernel_size, stride, dilation, transposed)
         feats = _conv_any_channels(feats, weight, kmap, transposed)
         if bias is not None:
             feats = feats + bias
-        output = SparseTensor(coords=input.cmaps[tensor_stride], feats=feats, stride=tensor_stride)
+        output = SparseTensor(coords=out_coords, feats=feats, stride=out_stride)
 
     output.cmaps = input.cmaps
     output.cmaps.setdefault(output.stride, output.coords)
