@@ -192,8 +192,10 @@ class SPVCNN(nn.Module):  # semantickitti/spvcnn.py:10-142
 def lovasz_grad(gt_sorted):  # criterions.py:40-52
     p = len(gt_sorted)
     gts = gt_sorted.sum()
-    intersection = gts - gt_sorted.float().cumsum(0)
-    union = gts + (1 - gt_sorted).float().cumsum(0)
+    # (the reference writes .float() here and below; the flags follow the probabilities' type instead, the same for fp32
+    # input, so that .double() input is evaluated in float64 throughout -- tests/test_host_loss_bound.py)
+    intersection = gts - gt_sorted.cumsum(0)
+    union = gts + (1 - gt_sorted).cumsum(0)
     jaccard = 1. - intersection / union
     if p > 1:
         jaccard[1:p] = jaccard[1:p] - jaccard[0:-1]
@@ -206,7 +208,7 @@ def lovasz_softmax_flat(probas, labels):  # criterions.py:73-101, classes='prese
     C = probas.size(1)
     losses = []
     for c in range(C):
-        fg = (labels == c).float()
+        fg = (labels == c).to(probas.dtype)
         if fg.sum() == 0:
             continue
         errors = (fg - probas[:, c]).abs()

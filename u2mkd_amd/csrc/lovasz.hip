@@ -3,8 +3,8 @@
 // The reference evaluates, per class c, errors = |fg_c - p_c| over the valid points, sorts them descending, and dots them with
 // the discrete gradient of the Jaccard index of the sorted foreground flags (lovasz_grad, criterions.py:40-52); the loss is the
 // mean over the classes that occur.  u2mkd_amd/losses.py evaluates all classes at once on the [C, P] transpose with ONE radix
-// sort of the composite key 4 c - error (float64: exact) -- but around that sort it queued ~45 element-wise torch launches per
-// call in the forward and ~18 in the backward, twice per KD step, right between the forward and the backward of the critical
+// sort of a composite key of class and error (float64, exact: lovasz_key) -- but around that sort it queued ~45 element-wise
+// torch launches per call in the forward and ~18 in the backward, twice per KD step, right between the forward and the backward of the critical
 // stream.  Here:
 //   lovasz_errors_kernel   probabilities [P, C] + labels -> errors [C, P] (-1 on ignored rows), sort keys [C, P] f64
 //   (torch.sort of the keys: rocPRIM's radix sort, value-dependent, stays in torch)
@@ -22,6 +22,15 @@ namespace u2mkd {
 
 constexpr int kLvThreads = 256;
 
+// Sort key of (class, error): class-major, error descending, the ignored rows (error -1) behind every valid one.  The bit pattern
+// of a float >= 0 grows with its value, so c 2^32 + (0x7F800000 - bits(e)) is an integer below 2^45 that orders the entries like
+// (c, -e) and is EXACT in double.  (4 c - e, the key before, is not: a double next to 4 resolves 9e-16, so for c >= 1 errors
+// below 1e-8 were merged with their neighbours and errors below 4e-16 with 0 -- saturated probabilities got the wrong rank.)
+__device__ __forceinline__ double lovasz_key(int c, float e) {
+    const int64_t r = e >= 0.f ? (int64_t)0x7F800000 - (int64_t)__float_as_uint(e) : (int64_t)0x7F800001;
+    return (double)(((int64_t)c << 32) + r);
+}
+
 __global__ void lovasz_errors_kernel(const float *__restrict__ probas, const int64_t *__restrict__ labels, int ignore,
                                      int64_t P, int C, float *__restrict__ errors, double *__restrict__ keys) {
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -32,7 +41,7 @@ __global__ void lovasz_errors_kernel(const float *__restrict__ probas, const int
         const float fg = (valid && lab == c) ? 1.f : 0.f;
         const float e = valid ? fabsf(fg - probas[p * C + c]) : -1.f;
         errors[(int64_t)c * P + p] = e;
-        keys[(int64_t)c * P + p] = (double)(4 * c) - (double)e;
+        keys[(int64_t)c * P + p] = lovasz_key(c, e);
     }
 }
 

@@ -38,13 +38,19 @@ def lovasz_softmax_flat(probas: torch.Tensor, labels: torch.Tensor, valid: torch
     if valid is not None:
         errors = torch.where(valid.unsqueeze(0), errors, errors.new_full((), -1.))
     # One flat sort instead of a row-wise one: torch answers sort(dim=1) of [17, 80 000] with ~77 merge-sort launches
-    # (0.65 ms on MI355X, twice per KD step, between the forward and the backward); the composite key 4c - error in
-    # float64 (exact: an integer plus a float32) orders class-major and error-descending in ONE radix sort, and block c of
-    # the result holds exactly the P entries of class c.
+    # (0.65 ms on MI355X, twice per KD step, between the forward and the backward); the composite key c 2^32 + (0x7F800000 -
+    # bits(error)) -- the bit pattern of a float32 >= 0 grows with its value; the ignored rows' -1 goes behind every valid
+    # error -- orders class-major and error-descending in ONE radix sort, and block c of the result holds exactly the P entries
+    # of class c.  (The key 4c - error in float64 that stood here is NOT exact: next to 4 a double resolves 9e-16, so small
+    # errors of the classes c >= 1 were merged with their neighbours or with 0.)  Other dtypes: a row-wise sort.
     with torch.no_grad():
         cls = torch.arange(C, device=probas.device).unsqueeze(1)
-        keys = (cls * 4).to(torch.float64) - errors.detach().to(torch.float64)
-        perm = torch.sort(keys.view(-1))[1].view(C, P) - cls * P
+        if errors.dtype == torch.float32:
+            e = errors.detach()
+            rank = torch.where(e >= 0, 0x7F800000 - e.contiguous().view(torch.int32).to(torch.int64), e.new_full((), 0x7F800001, dtype=torch.int64))
+            perm = torch.sort(((cls << 32) + rank).view(-1))[1].view(C, P) - cls * P
+        else:
+            perm = torch.sort(errors.detach(), dim=1, descending=True, stable=True)[1]
     errors_sorted = torch.gather(errors, 1, perm)
     fg_sorted = torch.gather(fg, 1, perm)
     if C * P < (1 << 24):
