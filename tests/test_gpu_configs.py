@@ -187,6 +187,47 @@ def test_geometry_in_slices_gives_the_step_the_same_geometry(hip, monkeypatch):
     assert torch.equal(a[2][0], b[2][0])               # the first step's teacher logits (later steps follow different students)
 
 
+def test_prefetch_loop_ending_without_prefetch_prepares_the_same_geometry_in_every_mode(hip, monkeypatch):
+    """train.KDStep with ``prefetch=`` over four steps, the last one with ``prefetch=None`` (an epoch's last batch: its forward
+    still waits for the geometry stream), in the three modes of train.NextBatch that prepare a batch ahead: in slices, in one
+    piece behind the backward, and in line in front of the backward (bf16 autocast: no side streams).  The same voxel
+    coordinates for every prepared batch in all three; between the two fp32 modes the first step's teacher logits bit for
+    bit and the first loss within rounding (the student's float atomics, as in the test above); the bf16 run is compared on
+    geometry only."""
+    from u2mkd_amd import train as T
+    from u2mkd_amd.synth import synth_kd_batch
+    batches = [T.kd_batch_to_device(synth_kd_batch(3000 + 500 * i, 1, seed=31 + i, image_hw=(64, 112))) for i in range(3)]
+
+    def run(mode):
+        monkeypatch.setenv('U2MKD_STAGED_GEOMETRY', '1' if mode == 'slices' else '0')
+        runner = _runner(1.0, 2.0, amp='bf16' if mode == 'inline' else False)
+        watch = T.TeacherWatch(runner.model.model_t)
+        losses, geo = [], []
+        cur = T.fresh_batch(batches[0])
+        for i in range(4):
+            nxt = T.fresh_batch(batches[(i + 1) % 3]) if i < 3 else None
+            watch.key = i
+            losses.append(float(runner(cur, prefetch=nxt)))
+            assert runner.pipe.mode == (mode if i < 3 else 'none')
+            if nxt is None:
+                assert runner.pipe._queued is None and runner.pipe._geo_done is None
+            else:
+                g = runner.pipe._queued[1]
+                geo.append((g['student']['_geometry'][1].C.clone(), g['teacher']['_geometry'][1].C.clone()))
+            cur = nxt
+        torch.cuda.synchronize()
+        assert all(np.isfinite(losses)), (mode, losses)
+        return losses, geo, [t for _, t in watch.log]
+    a, b, c = run('slices'), run('behind_backward'), run('inline')
+    assert len(a[1]) == len(b[1]) == len(c[1]) == 3
+    for ga, gb, gc in zip(a[1], b[1], c[1]):
+        for ta, tb, tc in zip(ga, gb, gc):
+            assert torch.equal(ta, tb) and torch.equal(ta, tc)
+    print('PREFETCH-MODES first loss: slices %.9g, behind the backward %.9g' % (a[0][0], b[0][0]))
+    assert torch.equal(a[2][0], b[2][0])
+    assert abs(a[0][0] - b[0][0]) <= 1e-5 * abs(a[0][0]), (a[0], b[0])
+
+
 def test_teacher_issued_one_step_ahead_gives_the_same_teacher_and_the_same_first_loss(hip, monkeypatch):
     """kd.teacher_ahead (U2MKD_TEACHER_AHEAD: the frozen teacher's forward of batch k + 1 queued behind step k's backward, on
     the teacher's stream, picked up by TSDFull.forward of that batch): every batch's teacher logits bit for bit those of the

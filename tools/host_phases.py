@@ -25,9 +25,9 @@ def timed(obj, name, label):
     setattr(obj, name, wrap)
 
 
-timed(run.model, 'prepare', 'geometry of the next batch (incl. blocking reads)')
 from u2mkd_amd.torchsparse.nn import functional as spf
 import u2mkd_amd.train as T0
+timed(T0, 'drain', 'geometry of the next batch in one piece (incl. blocking reads)')      # (train.NextBatch's one-piece modes)
 timed(spf, 'wait_counts', '  of which: waiting for posted sizes (wait_counts)')
 _slice = [0]
 _real_adv = T0._advance_geometry

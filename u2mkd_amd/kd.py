@@ -21,8 +21,7 @@ from .fusion import Atten_Fusion_Conv, L2CFusion, c2l_gather, feature_fetch, l2c
 from .pixel_head import sampled_head_applies, sampled_pixel_logits
 from .lidar.blocks import (BasicConvolutionBlock, BasicDeconvolutionBlock, FusedSequential, PointBatchNorm1d, PointLinear,
                            ResidualBlock)
-from .lidar.point_voxel import (initial_voxelize, point_to_voxel, prepare_geometry, prepare_geometry_many, prepare_geometry_staged,
-                                voxel_to_point)
+from .lidar.point_voxel import drain, initial_voxelize, point_to_voxel, prepare_geometry, prepare_geometry_staged, voxel_to_point
 from .torchsparse.nn import functional as spf
 from .lidar.sphereformer import SphereFormer
 from .lidar.spvcnn_spformer import SPVCNN_SPFORMER
@@ -392,15 +391,9 @@ class TSDFull(nn.Module):
         train.KDStep for batch k+1 between the forward and the backward of step k: the GPU queue is short there (the
         forward is bound by the host's launch rate), so the waits are short, and the host then issues the next
         forward while step k's backward -- ~30 ms of queued kernels -- drains, instead of sitting in the next
-        forward's first synchronisation for as long."""
+        forward's first synchronisation for as long.  The one-piece form of ``prepare_staged``."""
         with torch.no_grad():
-            g_s, g_t = prepare_geometry_many([(in_mod['student']['lidar'], self.model_s.pres, self.model_s.vres, 'kd_student'),
-                                              (in_mod['teacher']['lidar'], self.model_t.pres, self.model_t.vres, _TEACHER_TAG)])
-            in_mod['student']['_geometry'] = g_s
-            in_mod['teacher']['_geometry'] = g_t
-            if spf.prefetch_plans_enabled():
-                self.model_s.prefetch_plans(in_mod['student'])
-        return in_mod
+            return drain(self.prepare_staged(in_mod))
 
     def prepare_staged(self, in_mod: dict):
         """``prepare`` as a generator that yields in front of each of its two host reads (point_voxel.prepare_geometry_staged):
@@ -430,27 +423,20 @@ class TSDFull(nn.Module):
             return ret
         main = torch.cuda.current_stream()
         stu_in = in_mod['student']
-        ahead = in_mod['teacher'].pop('_teacher_out', None)
-        if ahead is not None:
-            # the trainer queued this batch's teacher forward one step ahead (``teacher_ahead``, train.KDStep): nothing of the
-            # teacher is issued here, the host goes straight to the student
-            t = ahead
-            ret = {'stu': self.model_s(stu_in)}
-            main.wait_stream(side)
-            for v in _tensors(t):
-                v.record_stream(main)
-            ret['t'] = t
-            return ret
-        if _CAMERA_STREAM and self.training and _overlap_ok():
-            # the camera head first: its large kernels run while the host queues the teacher's ~1500 small ones
-            stu_in = dict(stu_in, _camera_head=self.model_s.camera_head(stu_in))
-        if 'teacher_after_camera' in _DEBUG_ORDER:      # (debug, NOTES N9: the teacher starts when the camera head has finished)
-            side.wait_stream(_side_stream(in_mod['teacher']['lidar'].F, 'camera'))
-        side.wait_stream(main)
-        with torch.cuda.stream(side), torch.no_grad():
-            t = self.model_t(in_mod['teacher'])
-        if 'student_after_teacher' in _DEBUG_ORDER:     # (debug: the student's LiDAR branch starts when the teacher has finished)
-            main.wait_stream(side)
+        # (a teacher forward the trainer queued one step ahead -- ``teacher_ahead``, train.KDStep: nothing of the teacher is
+        # issued here then, the host goes straight to the student)
+        t = in_mod['teacher'].pop('_teacher_out', None)
+        if t is None:
+            if _CAMERA_STREAM and self.training and _overlap_ok():
+                # the camera head first: its large kernels run while the host queues the teacher's ~1500 small ones
+                stu_in = dict(stu_in, _camera_head=self.model_s.camera_head(stu_in))
+            if 'teacher_after_camera' in _DEBUG_ORDER:      # (debug, NOTES N9: the teacher starts when the camera head has finished)
+                side.wait_stream(_side_stream(in_mod['teacher']['lidar'].F, 'camera'))
+            side.wait_stream(main)
+            with torch.cuda.stream(side), torch.no_grad():
+                t = self.model_t(in_mod['teacher'])
+            if 'student_after_teacher' in _DEBUG_ORDER:     # (debug: the student's LiDAR branch starts when the teacher has finished)
+                main.wait_stream(side)
         ret = {'stu': self.model_s(stu_in)}
         main.wait_stream(side)
         for v in _tensors(t):

@@ -135,7 +135,12 @@ def prepare_geometry_many(items):
     of every down-sampled level of every network (spf.DownsamplePyramid) together with the out-of-range flags -- where
     the one-network-at-a-time, one-level-at-a-time form stopped the host 6 times per network.  The work queued to the
     GPU and every result (voxel order, coordinates, kernel maps) are the same."""
-    stages = prepare_geometry_staged(items)
+    return drain(prepare_geometry_staged(items))
+
+
+def drain(stages):
+    """The one-piece form of a staged preparation (prepare_geometry_staged, kd.TSDFull.prepare_staged): every slice of the
+    generator in one go, in the caller's contexts; returns the generator's result."""
     try:
         while True:
             next(stages)

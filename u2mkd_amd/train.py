@@ -12,6 +12,7 @@ from . import deferred
 from . import distributed as D
 from . import kd as KD
 from . import torchsparse as ts
+from .lidar.point_voxel import drain, prepare_geometry_staged
 from .losses import MixLovaszCrossEntropy
 from .optim import FusedAdam, FusedAdamW, FusedSGD, GradScaler
 
@@ -73,7 +74,7 @@ def _advance_geometry(amp, geo, staged):
 
 
 def _staged_geometry() -> bool:
-    """The next batch's geometry in slices between the phases of the current step (KDStep.__call__) -- or in one piece behind
+    """The next batch's geometry in slices between the phases of the current step (NextBatch) -- or in one piece behind
     the backward.  U2MKD_STAGED_GEOMETRY=0 / 1 decides; otherwise slices exactly when the process runs on the runtime's 4
     hardware queues (a single-rank process, distributed.configure_runtime): with more queues the slices' stream gets a queue
     of its own and the step falls off a scheduling cliff (64 -> 105 ms, NOTES N9.11)."""
@@ -81,6 +82,111 @@ def _staged_geometry() -> bool:
     if env in ('0', '1'):
         return env == '1'
     return D.hardware_queues() <= 4
+
+
+def _prefetch_mode(prefetch, is_cuda, behind_backward) -> str:
+    """How a step prepares the batch after it, decided once per call: 'slices' (on the geometry stream, one slice in front
+    of each phase of the step: its two host reads fall behind the forward's and the backward's launch work and find their
+    counts ready), 'behind_backward' (on the geometry stream in one piece behind the backward's launches;
+    trainers that offer it), 'inline' (on the caller's stream between forward and backward) or 'none'."""
+    if prefetch is None:
+        return 'none'
+    if is_cuda and deferred.overlap_ok():
+        if _staged_geometry():
+            return 'slices'
+        if behind_backward:
+            return 'behind_backward'
+    return 'inline'
+
+
+def _same(a, b):
+    """The queued batch IS the batch a call receives: object identity, of a tuple's members for a batch handed over in parts."""
+    if isinstance(a, tuple) and isinstance(b, tuple):
+        return len(a) == len(b) and all(x is y for x, y in zip(a, b))
+    return a is b
+
+
+class NextBatch:
+    """The next-batch prefetch protocol of the two trainers: batch k+1 is prepared (its geometry: every host synchronisation
+    of a step) while step k runs, and the call that receives the identical batch object takes the result.  A trainer's
+    ``__call__`` runs ``begin``, ``start``, forward + loss, ``before_backward``, backward + optimizer, ``after_step``.
+
+    The two side-stream modes (``_prefetch_mode``) put the preparation's ~1 000 small kernels and its two host round trips
+    on the geometry stream, underneath the step's large kernels instead of between forward and backward with the main
+    stream idle.  Memory: the side stream's allocations are consumed on the other streams one step later and freed there.
+    Ordering: (a) the next forward waits for ``_geo_done``, whatever that call's own mode -- also with ``prefetch=None`` on
+    an epoch's last batch; (b) this batch's geometry is kept alive for one more step (``_geo_keep``), until the next call
+    has queued its forward; (c) the side stream starts a preparation only behind ``entry``, the main stream's position when
+    THIS call began; (d) every tensor of the prepared batch is registered with the streams that will read it
+    (``record_stream``: ~200 tensors, ~0.2 ms of host time a step), so whenever it is freed the allocator itself holds the
+    block until those streams have passed that point.
+
+    ``in_mod_of(batch)``: the network's input of a batch;  ``stage(in_mod)``: a generator of three slices that prepares it
+    (point_voxel.prepare_geometry_staged) and returns it -- every mode runs this generator, the one-piece modes drain it;
+    ``roots(in_mod)``: the objects whose tensors (``_tensors_of``, one walk per root) are registered with ``readers(ref)``,
+    the streams that read them;  ``hook(in_mod, entry, geo_done, *hook_args)``: run behind slice 3 of the 'slices' mode."""
+
+    def __init__(self, amp, in_mod_of, stage, roots, readers, behind_backward=False, hook=None):
+        self.amp, self.in_mod_of, self.stage, self.roots, self.readers = amp, in_mod_of, stage, roots, readers
+        self.behind_backward, self.hook = behind_backward, hook
+        self._queued = self._geo_done = self._geo_keep = None
+        self.mode, self._staged, self._ref = 'none', None, None
+
+    def begin(self, batch, prefetch, ref):
+        """The ``in_mod`` of ``batch``: the queued one if ``batch`` is what the previous call was told to expect.  ``ref``:
+        a tensor of the batch (its device)."""
+        queued, self._queued = self._queued, None
+        self.mode = _prefetch_mode(prefetch, ref.is_cuda, self.behind_backward)
+        side = self.mode in ('slices', 'behind_backward')
+        self.entry = torch.cuda.current_stream().record_event() if side else None
+        if self._geo_done is not None:
+            torch.cuda.current_stream().wait_event(self._geo_done)
+            self._geo_done = None
+        self._prefetch, self._ref = prefetch, (ref if side else None)
+        return queued[1] if queued is not None and _same(queued[0], batch) else self.in_mod_of(batch)
+
+    def _geo_stream(self):
+        self._geo = KD._side_stream(self._ref, 'geo')
+        self._geo.wait_event(self.entry)
+
+    def _slice(self):
+        return _advance_geometry(self.amp, self._geo, self._staged)
+
+    def start(self):
+        if self.mode == 'slices':
+            self._geo_stream()
+            self._staged = self.stage(self.in_mod_of(self._prefetch))
+            self._slice()                  # slice 1: point hashes, voxel sets (launches only)
+
+    def before_backward(self):
+        if self.mode == 'slices':
+            self._slice()                  # read 1 (ready), slice 2: the down-sampled levels
+        elif self.mode == 'inline':
+            with self.amp.autocast(), torch.no_grad():
+                self._queued = (self._prefetch, drain(self.stage(self.in_mod_of(self._prefetch))))
+
+    def after_step(self, in_mod, *hook_args):
+        """``in_mod``: what this step ran on;  ``hook_args``: handed on to the hook."""
+        if self.mode == 'slices':
+            done = self._slice()           # read 2 (ready), slice 3: kernel maps, schedules
+        elif self.mode == 'behind_backward':
+            self._geo_stream()
+            with torch.cuda.stream(self._geo), self.amp.autocast(), torch.no_grad():
+                done = drain(self.stage(self.in_mod_of(self._prefetch)))
+        else:
+            return
+        self._queued = (self._prefetch, done)
+        self._geo_done = self._geo.record_event()
+        self._geo_keep = in_mod
+        if self.hook is not None and self.mode == 'slices':
+            self.hook(done, self.entry, self._geo_done, *hook_args)
+        users = self.readers(self._ref)
+        for root in self.roots(done):
+            for t in _tensors_of(root):
+                for st in users:
+                    t.record_stream(st)    # allocated on the side stream, read (and freed) on these
+        self._staged = self._ref = None
+
 
 class _Amp:
     """``amp.autocast(enabled)`` + ``amp.GradScaler(enabled)`` of the reference trainers
@@ -137,61 +243,38 @@ class LidarStep:
         self.opt = optimizer(self.net) if optimizer is not None else \
             make_optimizer([p for p in self.net.parameters() if p.requires_grad])
         self.sched = scheduler(self.opt) if scheduler is not None else _scheduler(self.opt, num_epochs, batch_size)
+        # (closures over the model, not over this trainer: no reference cycle keeps a dropped trainer's memory until a collection)
+        def stage(nxt):
+            nxt['_geometry'] = (yield from prepare_geometry_staged([(nxt['lidar'], model.pres, model.vres)]))[0]
+            return nxt
+        self.pipe = NextBatch(self.amp, lambda b: {'lidar': ts.SparseTensor(*b)}, stage, self._roots, self._readers)
+
+    @staticmethod
+    def _roots(nxt):
+        return [nxt['_geometry']]
+
+    @staticmethod
+    def _readers(ref):
+        return [torch.cuda.current_stream()]
 
     def __call__(self, feats, coords, targets, keyframe_mask=None, prefetch=None):
         """One training step.  ``prefetch`` = (feats, coords) of the NEXT batch (the tensors the next call will receive):
         its geometry -- voxel set and kernel maps, every host synchronisation of a step (point_voxel.prepare_geometry) --
-        is built between this step's forward and backward, and the next call issues its forward without waiting for the
-        GPU (as KDStep does)."""
+        is built while this step runs (``NextBatch``: in slices on a side stream, or between this step's forward and
+        backward), and the next call issues its forward without waiting for the GPU (as KDStep does)."""
         deferred.begin_step()      # (nothing of a backward pass that raised stays booked)
         deferred.set_reduced_precision(self.amp.enabled)      # (library kernels in bf16 / fp16: no side streams, deferred.overlap_ok)
-        queued = self.__dict__.pop('_queued', None)
-        if getattr(self, '_geo_done', None) is not None:
-            # whichever branch this call takes (prefetch=None on an epoch's last batch, staging switched off), the forward
-            # reads kernel maps the previous call built on the geometry stream: order the main stream behind them first
-            torch.cuda.current_stream().wait_event(self._geo_done)
-            self._geo_done = None
-        in_mod = {'lidar': ts.SparseTensor(feats, coords)}
-        if queued is not None and queued[0] is feats and queued[1] is coords:
-            in_mod = queued[2]
-        staged = None
-        if prefetch is not None and feats.is_cuda and deferred.overlap_ok() and _staged_geometry():
-            # the next batch's geometry in slices on a side stream, one in front of each phase of this step (as KDStep does,
-            # see there): its two size reads find their counts ready instead of waiting behind the forward's kernels
-            from .lidar.point_voxel import prepare_geometry_staged
-            main = torch.cuda.current_stream()
-            entry = main.record_event()
-            geo = KD._side_stream(feats, 'geo')
-            geo.wait_event(entry)
-            nf, nc = prefetch
-            nxt = {'lidar': ts.SparseTensor(nf, nc)}
-            staged = prepare_geometry_staged([(nxt['lidar'], self.model.pres, self.model.vres)])
-            _advance_geometry(self.amp, geo, staged)
+        in_mod = self.pipe.begin((feats, coords), None if prefetch is None else tuple(prefetch), feats)
+        self.pipe.start()
         with self.amp.autocast():
             out = self.net(in_mod)['x_vox']
             if keyframe_mask is not None:
                 out, targets = out[keyframe_mask], targets[keyframe_mask]
             loss = self.criterion(out, targets)
-        if staged is not None:
-            _advance_geometry(self.amp, geo, staged)
-            self.amp.backward_and_step(loss, self.opt)
-            self.sched.step()
-            nxt['_geometry'] = _advance_geometry(self.amp, geo, staged)[0]
-            self._queued = (nf, nc, nxt)
-            self._geo_done = geo.record_event()
-            self._geo_keep = in_mod              # (this batch's geometry lives until the next call has queued its forward)
-            for t in _tensors_of(nxt['_geometry']):
-                t.record_stream(main)            # allocated on the side stream, read (and freed) on the caller's
-            return loss.detach()
-        if prefetch is not None:
-            from .lidar.point_voxel import prepare_geometry
-            nf, nc = prefetch
-            nxt = {'lidar': ts.SparseTensor(nf, nc)}
-            with self.amp.autocast(), torch.no_grad():
-                nxt['_geometry'] = prepare_geometry(nxt['lidar'], self.model.pres, self.model.vres)
-            self._queued = (nf, nc, nxt)
+        self.pipe.before_backward()
         self.amp.backward_and_step(loss, self.opt)
         self.sched.step()
+        self.pipe.after_step(in_mod)
         return loss.detach()
 
     @torch.no_grad()
@@ -350,13 +433,34 @@ class KDStep:
         self.opt = optimizer(self.net) if optimizer is not None else \
             make_optimizer([p for p in self.net.parameters() if p.requires_grad])
         self.sched = scheduler(self.opt) if scheduler is not None else _scheduler(self.opt, num_epochs, batch_size)
+        amp = self.amp
+
+        def teacher_ahead(nxt, entry, geo_done, after_bwd):
+            # the next batch's frozen-teacher forward, queued NOW: the GPU is still running this step's backward, the host
+            # would otherwise arrive at the next step's start with the teacher's ~1 000 launches ahead of the student's
+            with amp.autocast():
+                KD.teacher_ahead(model, nxt, after=(entry, geo_done, after_bwd))
+        # (closures over the model, as in LidarStep; `prepare_staged` looked up per call: tools replace it on the model)
+        self.pipe = NextBatch(amp, self._in_mod, lambda in_mod: model.prepare_staged(in_mod), self._roots, self._readers,
+                              behind_backward=True, hook=teacher_ahead)
+
+    @staticmethod
+    def _roots(nxt):
+        # (the geometry, and the point <-> pixel plans kd.StudentMSP2IFM.prefetch_plans hung on the batch's masks)
+        return [[nxt[key].get('_geometry'), nxt[key].get('masks')] for key in ('student', 'teacher')]
+
+    @staticmethod
+    def _readers(ref):
+        return [torch.cuda.current_stream(), KD._side_stream(ref, 'teacher'), KD._side_stream(ref, 'camera')]
+
+    @property
+    def _queued(self):
+        """(next batch, its prepared ``in_mod``) between two calls, as ``NextBatch`` holds it; None when nothing is queued."""
+        return self.pipe._queued
 
     def train_mode(self):
         self.model.train()
         self.model.model_t.eval()          # core/nusc_trainers.py:203-208
-
-    def _advance_geometry(self, geo, staged):
-        return _advance_geometry(self.amp, geo, staged)
 
     @staticmethod
     def _in_mod(d):
@@ -369,86 +473,23 @@ class KDStep:
 
     def __call__(self, d, prefetch=None):
         """One training step on batch ``d``.  ``prefetch`` = the NEXT batch (the dict the next call will receive): its
-        geometry (voxel sets, kernel maps: every host synchronisation of a step, kd.TSDFull.prepare) is built between
-        this step's forward and backward, where the GPU queue is short; the next call then issues its whole forward
-        without waiting for the GPU while this step's backward drains.  The work per batch is the same, it only moves
+        geometry (voxel sets, kernel maps: every host synchronisation of a step, kd.TSDFull.prepare) is built while this
+        step runs (``NextBatch``: on a side stream in slices or behind the backward, else between forward and backward);
+        the next call then issues its whole forward without waiting for the GPU while this step's backward drains.  The work per batch is the same, it only moves
         one step ahead, as a data loader's prefetch does."""
         deferred.begin_step()      # (nothing of a backward pass that raised stays booked)
         deferred.set_reduced_precision(self.amp.enabled)      # (library kernels in bf16 / fp16: no side streams, deferred.overlap_ok)
-        queued = self.__dict__.pop('_queued', None)
-        in_mod = queued[1] if (queued is not None and queued[0] is d) else self._in_mod(d)
-        entry = torch.cuda.current_stream().record_event() if d['s_feats'].is_cuda else None     # (see the geometry side stream below)
-        if getattr(self, '_geo_done', None) is not None:
-            torch.cuda.current_stream().wait_event(self._geo_done)
-            self._geo_done = None
-        staged = None
-        if prefetch is not None and d['s_feats'].is_cuda and deferred.overlap_ok() and _staged_geometry():
-            # The next batch's geometry in THREE slices on the side stream, one in front of each phase of this step: its two
-            # host reads then fall behind the forward's and the backward's launch work (25 + 30 ms of host time) and find
-            # their counts ready -- the step is bound by the host (tools/host_phases.py: host time = wall time), and the reads
-            # were 5-6 ms of it sitting in hipStreamSynchronize.  Same launches, same order, same stream as the one-piece form
-            # below; `entry`, `_geo_done`, `_geo_keep` and the record_stream registration as there.
-            geo = KD._side_stream(d['s_feats'], 'geo')
-            geo.wait_event(entry)
-            staged = self.model.prepare_staged(self._in_mod(prefetch))
-            self._advance_geometry(geo, staged)            # slice 1: point hashes, voxel sets (launches only)
+        in_mod = self.pipe.begin(d, prefetch, d['s_feats'])
+        self.pipe.start()
         with self.amp.autocast():
             out = self.net(in_mod)
             ld = KD.kd_losses(out, d['targets'], d['fov_mask'], d['inverse_map'], d['inds'], d['num_pts'], d['num_vox_t'],
                               self.crit, d['keyframe_mask_full'])
-        if staged is not None:
-            self._advance_geometry(geo, staged)            # read 1 (ready), slice 2: the down-sampled levels
-            self.amp.backward_and_step(ld['total'], self.opt)
-            self.sched.step()
-            after_bwd = torch.cuda.current_stream().record_event() if KD._TEACHER_AHEAD == 2 else None
-            done = self._advance_geometry(geo, staged)     # read 2 (ready), slice 3: kernel maps, schedules
-            self._queued = (prefetch, done)
-            self._geo_done = geo.record_event()
-            self._geo_keep = in_mod
-            # the next batch's frozen-teacher forward, queued NOW: the GPU is still running this step's backward, the host
-            # would otherwise arrive at the next step's start with the teacher's ~1 000 launches ahead of the student's
-            with self.amp.autocast():
-                KD.teacher_ahead(self.model, done, after=(entry, self._geo_done, after_bwd))
-            users = [torch.cuda.current_stream(), KD._side_stream(d['s_feats'], 'teacher'), KD._side_stream(d['s_feats'], 'camera')]
-            for key in ('student', 'teacher'):
-                nxt = self._queued[1][key]
-                # (the geometry, and the point <-> pixel plans kd.StudentMSP2IFM.prefetch_plans hung on the batch's masks)
-                for t in _tensors_of([nxt.get('_geometry'), nxt.get('masks')]):
-                    for st in users:
-                        t.record_stream(st)
-            return ld['total'].detach()
-        if prefetch is not None and d['s_feats'].is_cuda and deferred.overlap_ok():
-            # The next batch's geometry AFTER this step's backward has been issued, on a side stream: its ~1 000 small
-            # kernels (hash tables, kernel maps, voxel sets) and the two host round trips run underneath the backward's
-            # large kernels instead of between forward and backward with the main stream idle (same box: 77.9 -> 76.3 ms).
-            # Memory: the side stream's allocations are consumed on the other streams one step later and freed there.
-            # Ordering: (a) the next forward waits for `_geo_done`, (b) a batch's geometry is kept alive for one more step
-            # (`_geo_keep`), (c) the side stream starts a preparation only behind `entry`, the main stream's position when
-            # THIS call began; and (round 5) every tensor of the prepared geometry is registered with its reader streams
-            # (record_stream, below), so the allocator itself holds a freed block until they have passed.
-            self.amp.backward_and_step(ld['total'], self.opt)
-            self.sched.step()
-            geo = KD._side_stream(d['s_feats'], 'geo')
-            geo.wait_event(entry)
-            with torch.cuda.stream(geo), self.amp.autocast():
-                self._queued = (prefetch, self.model.prepare(self._in_mod(prefetch)))
-            self._geo_done = geo.record_event()
-            self._geo_keep = in_mod
-            # Round 5: the ownership argument above is no longer all there is -- every tensor of the prepared geometry is also
-            # REGISTERED with the streams that will read it (the caller's and the teacher's): whenever it is freed, the
-            # allocator holds its block until those streams have passed that point (~200 tensors, ~0.2 ms of host time a step)
-            users = [torch.cuda.current_stream(), KD._side_stream(d['s_feats'], 'teacher'), KD._side_stream(d['s_feats'], 'camera')]
-            for key in ('student', 'teacher'):
-                nxt = self._queued[1][key]
-                for t in _tensors_of([nxt.get('_geometry'), nxt.get('masks')]):
-                    for st in users:
-                        t.record_stream(st)
-            return ld['total'].detach()
-        if prefetch is not None:
-            with self.amp.autocast():
-                self._queued = (prefetch, self.model.prepare(self._in_mod(prefetch)))
+        self.pipe.before_backward()
         self.amp.backward_and_step(ld['total'], self.opt)
         self.sched.step()
+        after_bwd = torch.cuda.current_stream().record_event() if self.pipe.mode == 'slices' and KD._TEACHER_AHEAD == 2 else None
+        self.pipe.after_step(in_mod, after_bwd)
         return ld['total'].detach()
 
     @torch.no_grad()
