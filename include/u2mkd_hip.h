@@ -992,7 +992,9 @@ int u2mkd_bn2d_eval_forward(const float *x, const float *res, int64_t b, int32_t
                             const float *beta, float eps, int32_t relu, const float *running_mean,
                             const float *running_var, float *y, u2mkd_stream_t s);
 /* dx, dgamma = sum dy' * xhat, dbeta = sum dy', dres = dy' (dy' = dy masked by the fused ReLU, recomputed from x and
- * res); batch_stats = 0: the statistics were constants (evaluation mode), dx = dy' * gamma * invstd.              */
+ * res); batch_stats = 0: the statistics were constants (evaluation mode), dx = dy' * gamma * invstd.  The mask is that
+ * of the forward only on the forward's own invstd, bit for bit: after u2mkd_bn2d_eval_forward 1.f / sqrtf(running_var +
+ * eps) in fp32; a caller that keeps an invstd of another expression normalises with u2mkd_bn2d_apply on that tensor. */
 int u2mkd_bn2d_backward(const float *dy, const float *x, const float *res, int64_t b, int32_t c, int64_t hw,
                         const float *mean, const float *invstd, const float *gamma, const float *beta, int32_t relu,
                         int32_t batch_stats, void *workspace, float *dgamma, float *dbeta, float *dx,

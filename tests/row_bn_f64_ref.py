@@ -344,16 +344,17 @@ def forward_bound(f, se, gamma, beta, dtype, res=None, running=None, momentum=MO
     return out
 
 
-def backward_bound(dy, f, b, fb, se, gamma, dtype, world=1, n_slab_rows=None):
+def backward_bound(dy, f, b, fb, se, gamma, dtype, world=1, n_slab_rows=None, depth=None):
     """{'dx', 'dres', 'dgamma', 'dbeta' [, 'dx_alt', 'dres_alt']} next to backward64's values ``b`` (computed with
-    ``undecided`` = fb['undecided'] in the ReLU form); fb = forward_bound's result; ``n_slab_rows``: the largest rank's rows"""
+    ``undecided`` = fb['undecided'] in the ReLU form); fb = forward_bound's result; ``n_slab_rows``: the largest rank's rows;
+    ``depth``: Dn of step 7 for kernels of another shape than the row kernels' (tests/bn2d_f64_ref.py)"""
     u = U32
     n, c = f['n'], dy.shape[1]
     gd, _ = _affine(gamma, None, f['pre'])
     ag, eh, axh, und = gd.abs(), fb['eh'], f['xhat'].abs(), fb['undecided']
     ady_all = dy.double().abs()
     ady = ady_all * (b['live'] | und)
-    dn = sum_depth(n_slab_rows or n, c, world)
+    dn = sum_depth(n_slab_rows or n, c, world) if depth is None else depth
     u1, u2 = (ady_all * und).sum(0), (ady_all * (axh + eh) * und).sum(0)
     bdb = g_(dn) * ady.sum(0) + u1 + floor_ulp(b['dbeta'], torch.float32)
     bdg = (ady * eh).sum(0) + g_(dn + 1) * (ady * (axh + eh)).sum(0) + u2 + floor_ulp(b['dgamma'], torch.float32)

@@ -1,6 +1,7 @@
 """BatchNorm2d (+ReLU, +residual) of the camera branch on csrc/bn2d.hip against torch.nn.functional.batch_norm
 in fp64 on the CPU: outputs, all gradients, running statistics; and the SwiftNet-18 branch as a whole with the HIP
-BatchNorm against the same branch on torch.nn."""
+BatchNorm against the same branch on torch.nn.
+(Every kernel form under a derived elementwise float64 bound, with no element excluded: tests/test_gpu_bn2d_f64.py.)"""
 import copy
 
 import pytest

@@ -178,9 +178,12 @@ class _BatchNorm2dFunction(torch.autograd.Function):
             if track:       # (written through raw pointers: versions bumped as torch's in-place updates would)
                 torch._C._increment_version([t for t in (bn.running_mean, bn.running_var, bn.num_batches_tracked) if t is not None])
         else:
+            # ONE invstd for both passes: the backward recomputes the ReLU mask from the tensor saved here, so the forward
+            # applies that tensor (u2mkd_bn2d_eval_forward takes 1 / sqrtf(var + eps) in the kernel, an ulp off torch.rsqrt in
+            # some channels, and an element on the ReLU edge then had y > 0 with dres = 0, or the reverse)
             mean, invstd = bn.running_mean, torch.rsqrt(bn.running_var + bn.eps)
-            L.call('u2mkd_bn2d_eval_forward', L.ptr(x), L.ptr(res), b, c, hw, L.ptr(weight), L.ptr(bias), bn.eps, int(relu),
-                   L.ptr(bn.running_mean), L.ptr(bn.running_var), L.ptr(y), st)
+            L.call('u2mkd_bn2d_apply', L.ptr(x), L.ptr(res), b, c, hw, L.ptr(mean), L.ptr(invstd), L.ptr(weight), L.ptr(bias),
+                   int(relu), L.ptr(y), st)
         ctx.save_for_backward(x, weight, bias, res, mean, invstd)
         ctx.relu, ctx.batch_stats = bool(relu), batch_stats
         return y
