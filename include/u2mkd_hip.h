@@ -1079,6 +1079,53 @@ int u2mkd_adam_batch_amp(const int64_t *jobs, int32_t n_jobs, int64_t total_chun
 int u2mkd_debug_adam_stage(int32_t stage, int32_t form, const float *a, const float *b, const float *c, float scalar, float *out,
                            int64_t n, u2mkd_stream_t s);
 
+/* Loader geometry on the device (csrc/prep.hip; u2mkd_amd/data/device_prep.py): a batch of raw nuScenes samples -> the tensors
+ * data/nuscenes_lc.py computes in numpy.  Every floating-point operation is one IEEE multiply / add / divide in the order of
+ * the loader's formulas, never a fused multiply-add (the file is built with contraction off); integer atomics only.
+ * Batch tables (device int32): kseg [nb+1] key-frame point offsets of the samples, mseg [nb+1] sweep point offsets of the
+ * samples, sseg [n_sweeps+1] sweep point offsets of every sweep of the batch; nb <= 64.
+ * u2mkd_prep_sweep_compact: keep flags of the sweep points [m, 4] (dropped: |x| < 1 and |y| < 1) and their exclusive prefix sum
+ *   pos [m+1] (pos[m] = the number kept): a stable compaction.  workspace: u2mkd_prep_scan_workspace_bytes(m), kept for
+ *   u2mkd_prep_points.
+ * u2mkd_prep_points: the points of one network input.  Sample b = its key-frame points (promoted to double), then its kept
+ *   sweep points, each out[r] = ((x tm[r][0] + y tm[r][1]) + z tm[r][2]) + tm[r][3] with tm [n_sweeps, 4, 4] double; with
+ *   train != 0 rotated and scaled, o_c = ((x rot[0][c] + y rot[1][c]) + z rot[2][c]) * scale (par [nb, 10] = rot row-major,
+ *   scale) and flipped (flip [nb]: 1 -x, 2 -y, 3 both).  f32mode != 0: the points are rounded to float32 and the voxel is
+ *   rintf(p / (float)voxel_size), else rint(p / voxel_size) in double; round half to even.  Writes feats [cap, 4] float, vox
+ *   [cap, 4] int32 (voxel, sample), labels_full [cap] (sweep points: ignore_label) and kf [cap] bytes (1 = key-frame point)
+ *   unless NULL, the per-axis minima mn [nb, 3] (caller-initialised to INT32_MAX) and off [nb+1], the point offsets of the
+ *   samples.  cap >= nk + m.  m = 0 (pos = one zero): key-frame points only, e.g. the student.
+ * u2mkd_prep_project: per (camera, key-frame point) in double: two steps p = R p + t, two steps p = R^T (p - t), each row
+ *   ((a x + b y) + c z); mask0 = p.z > 1, q = K p, q /= q.z, u = q.x / (im_w - 1) * 2 - 1, v likewise; mask = mask0 and
+ *   -1 < u < 1 and -1 < v < 1.  cam [nb, ncam, 60] double = 4 x (R[9], t[3]), K[9], im_w - 1, im_h - 1, 0.  pc [ncam, nk, 2]
+ *   float, masks [ncam, nk] bytes, pt_with_img [nk] bytes (any camera).
+ * u2mkd_prep_voxel_keys: keys [cap] = (sample, x, y, z) of the min-subtracted voxels packed into an int64 (field widths:
+ *   u2mkd_prep_key_bits(0..2), sample: (3)), INT64_MAX behind off[nb]; *err |= 1 where an axis does not fit its field.
+ * u2mkd_prep_voxel_sets: from the STABLY sorted keys and their permutation: head flags, exclusive scan (rank [cap+1]),
+ *   inverse_map [cap] (voxel rank of every point within its sample), inds (first = smallest point index of every voxel, within
+ *   its sample), voxoff [nb+1] (voxel offsets of the samples), and the gather by inds of feats, coordinates (minimum
+ *   subtracted, sample index appended as the last column), labels, kf, pt_with_img (-> fov_o) and, for all cameras, masks and
+ *   pc: sample b's block [ncam, nv_b] starts at ncam * voxoff[b].  Optional pairs (kf, kf_o), (pt_with_img, fov_o),
+ *   (masks + pc, masks_o + pc_o) may be NULL.  workspace: u2mkd_prep_scan_workspace_bytes(cap). */
+size_t u2mkd_prep_scan_workspace_bytes(int64_t n);
+int32_t u2mkd_prep_key_bits(int32_t axis);
+int u2mkd_prep_sweep_compact(const float *sweep, int64_t m, void *workspace, int32_t *pos, u2mkd_stream_t s);
+int u2mkd_prep_points(const float *key, const int64_t *labels, int64_t nk, const float *sweep, int64_t m, const void *workspace,
+                      const int32_t *pos, const int32_t *kseg, const int32_t *mseg, const int32_t *sseg, int32_t n_sweeps,
+                      const double *tm, int32_t nb, const double *par, const int32_t *flip, int32_t train, int32_t f32mode,
+                      double voxel_size, int64_t ignore_label, float *feats, int32_t *vox, int64_t *labels_full, uint8_t *kf,
+                      int32_t *mn, int32_t *off, u2mkd_stream_t s);
+int u2mkd_prep_project(const float *key, int64_t nk, const int32_t *kseg, int32_t nb, int32_t ncam, const double *cam, float *pc,
+                       uint8_t *masks, uint8_t *pt_with_img, u2mkd_stream_t s);
+int u2mkd_prep_voxel_keys(const int32_t *vox, const int32_t *mn, const int32_t *off, int32_t nb, int64_t cap, int64_t *keys,
+                          int32_t *err, u2mkd_stream_t s);
+int u2mkd_prep_voxel_sets(const int64_t *skeys, const int64_t *perm, int64_t cap, void *workspace, int32_t *rank,
+                          const int32_t *off, int32_t nb, const float *feats, const int32_t *vox, const int32_t *mn,
+                          const int64_t *labels, const uint8_t *kf, const uint8_t *pt_with_img, const uint8_t *masks,
+                          const float *pc, int32_t ncam, int64_t nk, int64_t *inverse_map, int64_t *inds, float *feats_o,
+                          int32_t *coords_o, int64_t *labels_o, uint8_t *kf_o, uint8_t *fov_o, uint8_t *masks_o, float *pc_o,
+                          int32_t *voxoff, u2mkd_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

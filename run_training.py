@@ -2,7 +2,7 @@
 teacher, :27-116) do, on the HIP operators.  One script; the trainer follows `model.name` of the configuration.
 
     python run_training.py configs/nuscenes/train/spformer_tsd_full_ours_star.yaml --run-dir runs/kd \\
-        --model.in_channel_t 4 [--weight-path ckpt.pt] [--non-dist] [--max-iters K] [--synthetic N_VOXELS]
+        --model.in_channel_t 4 [--weight-path ckpt.pt] [--non-dist] [--max-iters K] [--synthetic N_VOXELS] [--device-prep]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 run_training.py CONFIG ...
 
 Same order of business as the reference: configuration (file, recursive defaults, command-line overrides), process
@@ -75,8 +75,16 @@ class SyntheticKD(torch.utils.data.Dataset):
         return {'_numpy': b, '_eval': synth_eval_feed(b, seed)}
 
 
-def to_device(collated):
+def to_device(collated, is_kd=True):
     """(training batch of train.KDStep, eval tensors) of one loader batch."""
+    if isinstance(collated, list):            # --device-prep: raw samples, the geometry runs on the GPU (data/device_prep.py)
+        from u2mkd_amd.data import device_prep
+        if is_kd:
+            return device_prep.prepare_kd_batch(collated, with_eval=True)
+        t = device_prep.prepare_lidar_batch(collated)
+        d = {'t_feats': t['feats'], 't_coords': t['coords'], 'targets_t': t['targets'], 'inverse_map': t['inverse_map'],
+             'keyframe_mask_full': t['keyframe_mask_full'], 'keyframe_mask': t['keyframe_mask']}
+        return d, {'t_inverse_batch': t['inverse_batch'], 'targets_mapped_t': t['targets_mapped']}
     if '_numpy' in collated:
         d = T.kd_batch_to_device(collated['_numpy'])
         return d, {k: _cuda(torch.from_numpy(np.asarray(v))) for k, v in collated['_eval'].items()}
@@ -142,6 +150,7 @@ def main(argv=None):
     ap.add_argument('--non-dist', action='store_true', help='single process (the reference spells this flag inverted)')
     ap.add_argument('--max-iters', type=int, default=0, help='stop every epoch (training and validation) after K batches')
     ap.add_argument('--synthetic', type=int, default=0, metavar='N_VOXELS', help='synthetic scenes instead of dataset.root')
+    ap.add_argument('--device-prep', action='store_true', help='loader workers deliver raw samples; the batch geometry runs on the GPU')
     ap.add_argument('--backend', default=None, help='process-group backend (default nccl = RCCL; gloo: several ranks on one GPU, tests)')
     args, opts = ap.parse_known_args(argv)
 
@@ -178,6 +187,11 @@ def main(argv=None):
         workers = 0
     else:
         dataset = builder.make_dataset(cfg, rng=np.random.default_rng(seed))
+    if args.device_prep:
+        if args.synthetic:
+            raise SystemExit('--device-prep prepares raw samples of the on-disk dataset: not with --synthetic')
+        from u2mkd_amd.data.nuscenes_lc import RawView
+        dataset = {split: RawView(ds) for split, ds in dataset.items()}
     flow = {}
     epoch_box = [1]                       # read by the workers when an epoch's iterator starts them
     for split, ds in dataset.items():
@@ -212,7 +226,7 @@ def main(argv=None):
         for i, c in enumerate(flow[split]):
             if args.max_iters and i >= args.max_iters:
                 break
-            yield to_device(c)
+            yield to_device(c, is_kd)
 
     def train_step(cur, nxt):
         d, ev = cur

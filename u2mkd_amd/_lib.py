@@ -209,6 +209,16 @@ SIGNATURES = {
     'u2mkd_devoxelize_plan_workspace_bytes': (C.c_size_t, [_i64, _i64]),
     'u2mkd_devoxelize_plan': (C.c_int, [_p, _p, _i64, _i64, _p, _p, _p, _p, _p]),
     'u2mkd_ti_weights': (C.c_int, [_p, _p, _i64, _f32, _p, _p, _p]),
+    # loader geometry on the device (csrc/prep.hip)
+    'u2mkd_prep_scan_workspace_bytes': (_sz, [_i64]),
+    'u2mkd_prep_key_bits': (_i32, [_i32]),
+    'u2mkd_prep_sweep_compact': (C.c_int, [_p, _i64, _p, _p, _p]),
+    'u2mkd_prep_points': (C.c_int, [_p, _p, _i64, _p, _i64, _p, _p, _p, _p, _p, _i32, _p, _i32, _p, _p, _i32, _i32, C.c_double,
+                                    _i64, _p, _p, _p, _p, _p, _p, _p]),
+    'u2mkd_prep_project': (C.c_int, [_p, _i64, _p, _i32, _i32, _p, _p, _p, _p, _p]),
+    'u2mkd_prep_voxel_keys': (C.c_int, [_p, _p, _p, _i32, _i64, _p, _p, _p]),
+    'u2mkd_prep_voxel_sets': (C.c_int, [_p, _p, _i64, _p, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i64]
+                                       + [_p] * 11),
 }
 
 # the window attention's strided entries on 16-bit rows (q, k, v, out, dout, dq, dk, dv: bf16 / fp16, strides in elements), declared in

@@ -20,6 +20,8 @@ LIB = os.path.join(LIBDIR, 'libu2mkd_hip.so')
 ARCH = 'gfx950'
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['-O3', f'--offload-arch={ARCH}', '-fPIC', '-std=c++17', '-Wall', '-Wno-unused-function']
+# prep.hip is compared bit for bit with numpy's elementwise arithmetic: no multiply-add may be fused (NOTES N30)
+FILE_FLAGS = {'prep.hip': ['-ffp-contract=off']}
 
 
 def sources():
@@ -38,7 +40,7 @@ def _compile(src, force):
     newest = max(os.path.getmtime(src), _deps_mtime())
     if not force and os.path.exists(obj) and os.path.getmtime(obj) >= newest:
         return obj, False
-    cmd = [HIPCC, *FLAGS, '-c', src, '-o', obj]
+    cmd = [HIPCC, *FLAGS, *FILE_FLAGS.get(os.path.basename(src), []), '-c', src, '-o', obj]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f'hipcc failed for {src}:\n{r.stdout}\n{r.stderr}')

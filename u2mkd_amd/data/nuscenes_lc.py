@@ -33,7 +33,7 @@ from ..torchsparse.utils.collate import sparse_collate
 from ..torchsparse.utils.quantize import sparse_quantize
 
 __all__ = ['NuScenesTables', 'LCNuScenesDataset', 'collate_fn', 'collated_to_kd_batch', 'quat_to_rot',
-           'transform_matrix', 'LABELS_MAPPING', 'CAM_CHANNELS']
+           'transform_matrix', 'LABELS_MAPPING', 'CAM_CHANNELS', 'raw_collate_fn', 'RawView']
 
 # core/datasets/lc_semantic_nusc_tsd_full.py:72-105: lidarseg class -> the 16 training classes (0 = ignore)
 LABELS_MAPPING = {1: 0, 5: 0, 7: 0, 8: 0, 10: 0, 11: 0, 13: 0, 19: 0, 20: 0, 0: 0, 29: 0, 31: 0, 9: 1, 14: 2, 15: 3,
@@ -299,6 +299,122 @@ class LCNuScenesDataset(torch.utils.data.Dataset):
         return {'feed_dict_s': feed_dict_s, 'feed_dict_t': feed_dict_t, 'lidar_token': lidar_token}
 
     collate_fn = staticmethod(lambda batch: collate_fn(batch))
+
+    # ---- raw samples for the device path (data/device_prep.py): file reads, table look-ups and random draws only
+    def _raw_sweeps(self, sample_ref, nsweeps, only_past=False):
+        """The sweeps ``_aggregate_lidar_sweeps`` walks (prev, then next), UNFILTERED and untransformed: their points
+        concatenated, ``seg`` [n+1] the point offsets, ``tm`` [n,4,4] the sweep -> key-frame transforms (the same numpy
+        products), ``lag`` [n] the time lags."""
+        nusc = self.nusc
+        ref_sd = nusc.get('sample_data', sample_ref['data']['LIDAR_TOP'])
+        ref_pose = nusc.get('ego_pose', ref_sd['ego_pose_token'])
+        ref_cs = nusc.get('calibrated_sensor', ref_sd['calibrated_sensor_token'])
+        ref_time = 1e-6 * ref_sd['timestamp']
+        ref_from_car = transform_matrix(ref_cs['translation'], ref_cs['rotation'], inverse=True)
+        car_from_global = transform_matrix(ref_pose['translation'], ref_pose['rotation'], inverse=True)
+
+        def walk(count, direction):
+            cur, out = ref_sd, []
+            for _ in range(count):
+                if cur[direction] == '':
+                    break
+                cur = nusc.get('sample_data', cur[direction])
+                p = np.fromfile(os.path.join(nusc.dataroot, cur['filename']), dtype=np.float32).reshape([-1, 5])[:, :4]
+                pose = nusc.get('ego_pose', cur['ego_pose_token'])
+                global_from_car = transform_matrix(pose['translation'], pose['rotation'])
+                cs = nusc.get('calibrated_sensor', cur['calibrated_sensor_token'])
+                car_from_current = transform_matrix(cs['translation'], cs['rotation'])
+                tm = reduce(np.dot, [ref_from_car, car_from_global, global_from_car, car_from_current])
+                lag = ref_time - 1e-6 * cur['timestamp'] if direction == 'prev' else 1e-6 * cur['timestamp'] - ref_time
+                out.append((p, tm, lag))
+            return out
+
+        prev = walk(nsweeps, 'prev')
+        nxt = [] if only_past else walk(2 * nsweeps - len(prev), 'next')
+        walked = prev + nxt
+        pts = [np.ascontiguousarray(p) for p, _, _ in walked]
+        return {'points': np.concatenate(pts, axis=0) if pts else np.zeros((0, 4), np.float32),
+                'seg': np.cumsum([0] + [p.shape[0] for p in pts]).astype(np.int32),
+                'tm': np.stack([tm for _, tm, _ in walked]).astype(np.float64) if walked else np.zeros((0, 4, 4)),
+                'lag': np.array([lag for _, _, lag in walked], dtype=np.float64)}
+
+    def _draw_rotation(self):
+        theta = self.rng.uniform(0, 2 * np.pi)
+        scale = self.rng.uniform(0.95, 1.05)
+        rot = np.array([[np.cos(theta), np.sin(theta), 0], [-np.sin(theta), np.cos(theta), 0], [0, 0, 1]])
+        return rot, float(scale)
+
+    def raw(self, index):
+        """What ``__getitem__(index)`` reads and draws, with none of its geometry done: the input of
+        ``device_prep.prepare_kd_batch``.  ``self.rng`` is consumed in ``__getitem__``'s order (teacher theta, scale, flip
+        kind; the dropped cameras; student theta, scale), so with equal seeds both describe the same sample.  numpy only: a
+        loader worker that calls this never opens the device."""
+        if self.debug:
+            raise NotImplementedError('raw(): debug (label_fov) is not served by the device path')
+        nusc = self.nusc
+        sample = self.sample[index]
+        lidar_token = sample['data']['LIDAR_TOP']
+        lidar_sd = nusc.get('sample_data', lidar_token)
+        pts = np.fromfile(os.path.join(nusc.dataroot, lidar_sd['filename']), dtype=np.float32).reshape([-1, 5])[:, :4]
+        if self.split == 'test':
+            labels = np.zeros(pts.shape[0], dtype=np.int64)
+        else:
+            seg = np.fromfile(os.path.join(nusc.dataroot, nusc.get('lidarseg', lidar_token)['filename']), dtype=np.uint8)
+            labels = _LABEL_LUT[seg]
+        train = 'train' in self.split
+        sweeps = self._raw_sweeps(sample, self.multisweeps, self.only_past) if self.multisweeps != 0 else None
+        teacher = {'rot': np.eye(3), 'scale': 1.0, 'flip': 0}
+        if train:
+            teacher['rot'], teacher['scale'] = self._draw_rotation()
+            if self.flip_aug:
+                teacher['flip'] = int(self.rng.integers(0, 4))
+        drop = self.rng.choice(len(CAM_CHANNELS), self.im_drop, replace=False) if train else []
+        cs_l = nusc.get('calibrated_sensor', lidar_sd['calibrated_sensor_token'])
+        pose_l = nusc.get('ego_pose', lidar_sd['ego_pose_token'])
+        f64 = lambda v: np.asarray(v, dtype=np.float64)
+        cams, images = [], []
+        for idx, channel in enumerate(CAM_CHANNELS):
+            if train and idx in drop:
+                continue
+            cam_sd = nusc.get('sample_data', sample['data'][channel])
+            im, (im_w, im_h) = self._load_image(os.path.join(nusc.dataroot, cam_sd['filename']))
+            images.append(im)
+            pose_c = nusc.get('ego_pose', cam_sd['ego_pose_token'])
+            cs_c = nusc.get('calibrated_sensor', cam_sd['calibrated_sensor_token'])
+            # lidar -> ego, ego -> global: p = R p + t; global -> ego (camera time), ego -> camera: p = R^T (p - t)
+            steps = [(quat_to_rot(r['rotation']), f64(r['translation'])) for r in (cs_l, pose_l, pose_c, cs_c)]
+            cams.append({'channel': idx, 'steps': steps, 'K': f64(cs_c['camera_intrinsic']), 'size': (im_w, im_h)})
+        student = {'rot': np.eye(3), 'scale': 1.0}
+        if train:
+            student['rot'], student['scale'] = self._draw_rotation()
+        return {'points': np.ascontiguousarray(pts), 'labels': labels, 'sweeps': sweeps, 'teacher': teacher, 'student': student,
+                'cams': cams, 'images': np.stack(images, axis=0), 'voxel_size': self.voxel_size, 'train': train,
+                'multisweeps': self.multisweeps, 'ignore_index': self.ignored_labels, 'lidar_token': lidar_token}
+
+    raw_collate_fn = staticmethod(lambda batch: raw_collate_fn(batch))
+
+
+class RawView(torch.utils.data.Dataset):
+    """``dataset`` served through ``raw()``: what a DataLoader iterates with ``--device-prep`` (its workers re-seed
+    ``.rng``, which is the wrapped dataset's)."""
+
+    def __init__(self, dataset):
+        self.dataset = dataset
+
+    rng = property(lambda self: self.dataset.rng, lambda self, v: setattr(self.dataset, 'rng', v))
+
+    def __len__(self):
+        return len(self.dataset)
+
+    def __getitem__(self, index):
+        return self.dataset.raw(index)
+
+    collate_fn = staticmethod(lambda batch: raw_collate_fn(batch))
+
+
+def raw_collate_fn(batch):
+    """The raw samples of a batch as a list, arrays untouched (``device_prep.prepare_kd_batch`` concatenates on upload)."""
+    return list(batch)
 
 
 def collate_fn(batch):

@@ -269,3 +269,58 @@ def synth_eval_feed(b, seed: int):
     return {'s_inverse_map': inv, 's_inverse_batch': ib, 'targets_mapped': rng.integers(0, 17, len(inv)),
             'label_fov': rng.integers(0, 17, len(inv)), 't_inverse_batch': tb,
             'targets_mapped_t': rng.integers(0, 17, len(tb))}
+
+
+def synth_raw_sample(n_key: int, sweep_sizes=None, seed: int = 0, cams=(0, 1, 2, 3, 4, 5), image_hw=(36, 64), voxel_size=0.05,
+                     train: bool = True, extent: float = 40.0):
+    """One raw sample in the schema of ``data.nuscenes_lc.LCNuScenesDataset.raw`` (the input of ``data.device_prep``) without a
+    dataset on disk: ``n_key`` key-frame points, one sweep per entry of ``sweep_sizes`` (None: no multi-sweep teacher) with a
+    small rigid motion each, the cameras ``cams`` of a six-camera ring, seeded augmentation draws."""
+    rng = np.random.default_rng(seed)
+
+    def cloud(n):
+        return np.concatenate([rng.uniform(-extent, extent, (n, 2)), rng.uniform(-2, 3, (n, 1)), rng.uniform(0, 255, (n, 1))],
+                              1).astype(np.float32)
+
+    def yaw(deg):
+        a = np.deg2rad(deg)
+        return np.array([[np.cos(a), -np.sin(a), 0], [np.sin(a), np.cos(a), 0], [0, 0, 1.0]])
+
+    def draw():
+        theta = rng.uniform(0, 2 * np.pi)
+        rot = np.array([[np.cos(theta), np.sin(theta), 0], [-np.sin(theta), np.cos(theta), 0], [0, 0, 1]])
+        return rot, float(rng.uniform(0.95, 1.05))
+
+    sweeps = None
+    if sweep_sizes is not None:
+        pts = [cloud(int(n)) for n in sweep_sizes]
+        tms = []
+        for k in range(len(pts)):
+            tm = np.eye(4)
+            tm[:3, :3] = yaw(rng.uniform(-3, 3))
+            tm[:3, 3] = [rng.uniform(-2, 2), rng.uniform(-0.5, 0.5), rng.uniform(-0.05, 0.05)]
+            tms.append(tm)
+        sweeps = {'points': np.concatenate(pts, 0) if pts else np.zeros((0, 4), np.float32),
+                  'seg': np.cumsum([0] + [p.shape[0] for p in pts]).astype(np.int32),
+                  'tm': np.stack(tms) if tms else np.zeros((0, 4, 4)), 'lag': 0.05 * (1.0 + np.arange(len(pts)))}
+    teacher = {'rot': np.eye(3), 'scale': 1.0, 'flip': 0}
+    student = {'rot': np.eye(3), 'scale': 1.0}
+    if train:
+        teacher['rot'], teacher['scale'] = draw()
+        teacher['flip'] = int(rng.integers(0, 4))
+        student['rot'], student['scale'] = draw()
+    lidar = (np.array([[0, 1, 0], [-1, 0, 0], [0, 0, 1.0]]), np.array([0.9, 0.0, 1.8]))
+    pose_l = (yaw(3.0), np.array([100.0, 50.0, 0.0]))
+    pose_c = (yaw(3.1), np.array([100.1, 50.01, 0.0]))
+    ring = [55.0, 0.0, -55.0, 110.0, 180.0, -110.0]
+    cam_list = []
+    for c in cams:
+        a = np.deg2rad(ring[c])
+        fwd, left, up = np.array([np.cos(a), np.sin(a), 0.0]), np.array([-np.sin(a), np.cos(a), 0.0]), np.array([0, 0, 1.0])
+        cam_list.append({'channel': int(c), 'steps': [lidar, pose_l, pose_c, (np.stack([-left, -up, fwd], axis=1), np.array([1.5, 0.1, 1.5]))],
+                         'K': np.array([[1266.0, 0.0, 816.0], [0.0, 1266.0, 491.0], [0.0, 0.0, 1.0]]), 'size': (1600, 900)})
+    h, w = image_hw
+    return {'points': cloud(n_key), 'labels': rng.integers(0, 17, n_key).astype(np.int64), 'sweeps': sweeps, 'teacher': teacher,
+            'student': student, 'cams': cam_list, 'images': rng.integers(0, 255, (len(cam_list), h, w, 3), dtype=np.uint8),
+            'voxel_size': voxel_size, 'train': train, 'multisweeps': 0 if sweep_sizes is None else 1,          # (the dataset's setting: only "0 or not" matters downstream)
+            'ignore_index': 0, 'lidar_token': 'synthetic-%d' % seed}
