@@ -1126,6 +1126,31 @@ int u2mkd_prep_voxel_sets(const int64_t *skeys, const int64_t *perm, int64_t cap
                           int32_t *coords_o, int64_t *labels_o, uint8_t *kf_o, uint8_t *fov_o, uint8_t *masks_o, float *pc_o,
                           int32_t *voxoff, u2mkd_stream_t s);
 
+/* Test-time voting tail (csrc/vote.hip; u2mkd_amd/evaluate.py: vote_point_predictions) -- what NuScenes_Evaluator._run_step does
+ * behind the model (core/nusc_trainers.py:523-550) in one launch that reads every size and offset on the device.
+ * A batch holds n_scans scans with n_votes copies each: copy (s, v) is sample b = s * n_votes + v of the device batch,
+ * n_scans * n_votes <= 64.  logits [Nv, c] voxel rows (row_type: 0 = fp32, 1 = bf16, 2 = fp16, anything else is an error),
+ * inverse_map [Np_all] the voxel rank of every point within its sample, copy_point_off / copy_voxel_off [n_scans * n_votes] each
+ * copy's first point row / first voxel row, scan_seg [n_scans + 1] the key-frame point offsets of the scans in the OUTPUT
+ * (scan_seg[0] = 0, P = scan_seg[n_scans]).  A sample's key-frame points come first (u2mkd_prep_points), so key-frame point j of
+ * scan s is row copy_point_off[s * n_votes + v] + j of every copy; the sweep points behind them are never read.
+ *   sums [P, c] fp32 (may be NULL): sum[p][k] = (((0 + x_0) + x_1) + ... + x_{V-1}) in fp32 in vote order, x_v =
+ *     logits[copy_voxel_off[b] + inverse_map[copy_point_off[b] + j]][k] widened exactly -- additions only;
+ *   pred [P] int64: the lowest class index among the maxima of sum[p]; a NaN is maximal (the first NaN wins), as torch.argmax on
+ *     the CPU; class skip_class is left out when skip_class >= 0 (then c >= 2 and skip_class < c);
+ *   counts [3, c] int64 (may be NULL, then targets may be NULL too), ADDED to: over the points with targets[p] != ignore_label,
+ *     row 0 the targets seen, row 1 the correct predictions, row 2 the predictions, per class (MeanIoU.after_step's three
+ *     bincounts).  A target outside [0, c) that is not ignore_label is counted NOWHERE: not seen, not correct, and its point's
+ *     prediction is not counted either.  Per-workgroup integer histograms, then integer atomics: the result does not depend on
+ *     any order.
+ * 1 <= c <= 64, n_votes >= 1; anything else is an error before any launch.  n_scans = 0 launches nothing; otherwise the point
+ * count is known to the device alone: a fixed grid walks the points and does nothing for an empty scan or P = 0.  The offsets
+ * and inverse_map are trusted (every row they name must exist). */
+int u2mkd_vote_points(const void *logits, int32_t row_type, int32_t c, const int64_t *inverse_map, const int32_t *copy_point_off,
+                      const int32_t *copy_voxel_off, const int32_t *scan_seg, int32_t n_scans, int32_t n_votes,
+                      const int64_t *targets, int64_t ignore_label, int32_t skip_class, float *sums, int64_t *pred, int64_t *counts,
+                      u2mkd_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -219,6 +219,8 @@ SIGNATURES = {
     'u2mkd_prep_voxel_keys': (C.c_int, [_p, _p, _p, _i32, _i64, _p, _p, _p]),
     'u2mkd_prep_voxel_sets': (C.c_int, [_p, _p, _i64, _p, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i64]
                                        + [_p] * 11),
+    # test-time voting tail (csrc/vote.hip)
+    'u2mkd_vote_points': (C.c_int, [_p, _i32, _i32, _p, _p, _p, _p, _i32, _i32, _p, _i64, _i32, _p, _p, _p, _p]),
 }
 
 # the window attention's strided entries on 16-bit rows (q, k, v, out, dout, dq, dk, dv: bf16 / fp16, strides in elements), declared in

@@ -128,7 +128,7 @@ def _parse_overrides(opts):
     return out
 
 
-def make_dataset(cfg, dataset_name=None, tables=None, rng=None) -> dict:
+def make_dataset(cfg, dataset_name=None, tables=None, rng=None, splits=('train', 'val')) -> dict:
     """core/builder.py:17-127, the branch of the KD path: `lc_semantic_nusc_tsd_full` -> {'train', 'val'} of the
     LiDAR + camera loader (core/datasets/lc_semantic_nusc_tsd_full.py:60-67) with the keys its constructor reads from
     the configuration (:131-158).  ``tables``: an opened data.NuScenesTables (default: `dataset.root`, version
@@ -149,7 +149,7 @@ def make_dataset(cfg, dataset_name=None, tables=None, rng=None) -> dict:
                   multisweeps=sweeps.get('num_sweeps', 0), only_past=sweeps.get('only_past', False),
                   ignore_index=cfg.criterion.ignore_index, debug=cfg.get('debug', {}).get('debug_val', False), rng=rng)
     out = {}
-    for split in ('train', 'val'):
+    for split in splits:                   # ('test', run_evaluation.py: no labels, no official index file -- every sample)
         idx_file = os.path.join('data', 'nuscenes', 'nuscenes_%s_official.npy' % split)
         select = np.load(idx_file) if os.path.isfile(idx_file) else None
         out[split] = data.LCNuScenesDataset(tables, split=split, select_idx=select, **common)

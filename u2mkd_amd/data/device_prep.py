@@ -92,9 +92,21 @@ class _Uploaded:
         self.cam = f64[cut[3]:cut[4]] if cameras else None
         # int32: kseg, mseg, sseg, the teacher's flip kinds, zeros (the student's)
         tables = [kseg, mseg, sseg, [int(r['teacher']['flip']) for r in raws], np.zeros(nb + 1), np.zeros(1)]
+        # a voting batch (nuscenes_lc.VoteBatch: copy v of scan s is sample s * num_vote + v): the scans' key-frame point
+        # offsets in the voted output ride in the same upload
+        self.num_vote = getattr(raws, 'num_vote', None)
+        if self.num_vote:
+            nv = self.num_vote
+            if nb % nv or any(nks[b] != nks[b - b % nv] or raws[b].get('lidar_token') != raws[b - b % nv].get('lidar_token')
+                              for b in range(nb)):
+                raise ValueError('device_prep: a voting batch holds %d copies of every scan, each with the same key-frame points' % nv)
+            self.scan_nk, self.kseg_host = nks[::nv], [int(k) for k in kseg]
+            tables.append(np.cumsum([0] + self.scan_nk))
         i32 = _up(np.concatenate([np.asarray(t, np.int64) for t in tables]).astype(np.int32), dev, self._host)
         cut = np.cumsum([0] + [len(t) for t in tables])
         self.kseg, self.mseg, self.sseg, self.flip, self.zeros, self.zero = (i32[cut[i]:cut[i + 1]] for i in range(6))
+        self.scan_seg = i32[cut[6]:cut[7]] if self.num_vote else None
+        self.tokens = [r.get('lidar_token') for r in raws]
         self.images = _up(np.stack([r['images'] for r in raws]), dev, self._host) if cameras else None
         self.dev = dev
 
@@ -194,9 +206,22 @@ def _sample_of(offsets, n, dev):
     return torch.from_numpy(rows).to(dev)
 
 
+def _vote_tables(u, st, inverse_map):
+    """The tables ``evaluate.vote_point_predictions`` takes for the network input ``st`` of a voting batch: views of the
+    counts the kernels wrote (``off`` / ``voxoff``: every copy's first point and first voxel row) and the uploaded
+    ``scan_seg``; the targets are vote 0's key-frame labels of every scan.  Everything stays on the device."""
+    nv, k = u.num_vote, u.kseg_host
+    firsts = range(0, u.nb, nv)
+    targets = [u.labels[k[b]:k[b + 1]] for b in firsts]
+    return {'num_vote': nv, 'copy_point_off': st.off[:u.nb], 'copy_voxel_off': st.voxoff[:u.nb], 'scan_seg': u.scan_seg,
+            'inverse_map': inverse_map, 'targets': targets[0] if len(targets) == 1 else torch.cat(targets),
+            'num_pts': list(u.scan_nk), 'lidar_tokens': [u.tokens[b] for b in firsts]}
+
+
 def prepare_kd_batch(raws, device='cuda', with_eval=False):
     """Raw samples (``LCNuScenesDataset.raw``; a ``raw_collate_fn`` batch) -> the device batch ``train.KDStep`` takes, on the
-    current stream.  ``with_eval``: also the tensors of the eval branch (run_training.kd_eval_feed) as a second dict."""
+    current stream.  ``with_eval``: also the tensors of the eval branch (run_training.kd_eval_feed) as a second dict.
+    A ``VoteBatch`` (``VoteView``'s collate) additionally gets ``'vote'``: the student input's voting tables."""
     dev = _require_device(device)
     u = _Uploaded(raws, dev, cameras=True)
     tea = _points(u, teacher=True)
@@ -222,6 +247,8 @@ def prepare_kd_batch(raws, device='cuda', with_eval=False):
     }
     if tea.kf_o is not None:
         out['keyframe_mask'] = tea.kf_o[:nvt]
+    if u.num_vote:
+        out['vote'] = _vote_tables(u, stu, stu.inverse_map[:u.nk])
     if not with_eval:
         return out
     ev = {'s_inverse_map': stu.inverse_map[:u.nk], 's_inverse_batch': _sample_of(s_off, u.nk, dev),
@@ -232,7 +259,7 @@ def prepare_kd_batch(raws, device='cuda', with_eval=False):
 
 def prepare_lidar_batch(raws, device='cuda'):
     """The teacher-only trainer's batch (``train.LidarStep`` and its ``evaluate``) from the same raw samples: the teacher
-    half alone -- no projection, no images."""
+    half alone -- no projection, no images.  A ``VoteBatch`` additionally gets ``'vote'``: the teacher input's voting tables."""
     dev = _require_device(device)
     u = _Uploaded(raws, dev, cameras=False)
     tea = _points(u, teacher=True)
@@ -240,9 +267,12 @@ def prepare_lidar_batch(raws, device='cuda'):
     (t_off, t_vox), = _read(u, [tea])
     nb = u.nb
     nvt, npt = t_vox[nb], t_off[nb]
-    return {'feats': tea.feats_o[:nvt], 'coords': tea.coords_o[:nvt], 'targets': tea.labels_o[:nvt],
-            'keyframe_mask': tea.kf_o[:nvt] if tea.kf_o is not None else None,
-            'keyframe_mask_full': tea.kf[:npt] if tea.kf is not None else None,
-            'inverse_map': tea.inverse_map[:npt], 'inverse_batch': _sample_of(t_off, npt, dev),
-            'targets_mapped': tea.labels[:npt], 'num_pts': [t_off[b + 1] - t_off[b] for b in range(nb)],
-            'num_vox': [t_vox[b + 1] - t_vox[b] for b in range(nb)]}
+    out = {'feats': tea.feats_o[:nvt], 'coords': tea.coords_o[:nvt], 'targets': tea.labels_o[:nvt],
+           'keyframe_mask': tea.kf_o[:nvt] if tea.kf_o is not None else None,
+           'keyframe_mask_full': tea.kf[:npt] if tea.kf is not None else None,
+           'inverse_map': tea.inverse_map[:npt], 'inverse_batch': _sample_of(t_off, npt, dev),
+           'targets_mapped': tea.labels[:npt], 'num_pts': [t_off[b + 1] - t_off[b] for b in range(nb)],
+           'num_vox': [t_vox[b + 1] - t_vox[b] for b in range(nb)]}
+    if u.num_vote:
+        out['vote'] = _vote_tables(u, tea, out['inverse_map'])
+    return out

@@ -33,7 +33,7 @@ from ..torchsparse.utils.collate import sparse_collate
 from ..torchsparse.utils.quantize import sparse_quantize
 
 __all__ = ['NuScenesTables', 'LCNuScenesDataset', 'collate_fn', 'collated_to_kd_batch', 'quat_to_rot',
-           'transform_matrix', 'LABELS_MAPPING', 'CAM_CHANNELS', 'raw_collate_fn', 'RawView']
+           'transform_matrix', 'LABELS_MAPPING', 'CAM_CHANNELS', 'raw_collate_fn', 'RawView', 'VoteView', 'VoteBatch', 'draw_sample_parameters']
 
 # core/datasets/lc_semantic_nusc_tsd_full.py:72-105: lidarseg class -> the 16 training classes (0 = ignore)
 LABELS_MAPPING = {1: 0, 5: 0, 7: 0, 8: 0, 10: 0, 11: 0, 13: 0, 19: 0, 20: 0, 0: 0, 29: 0, 31: 0, 9: 1, 14: 2, 15: 3,
@@ -110,6 +110,24 @@ class NuScenesTables:
 
 def _rotate_points(p3n: np.ndarray, rm: np.ndarray) -> np.ndarray:
     return rm.dot(p3n)
+
+
+def draw_sample_parameters(rng, flip_aug=True, im_drop=0):
+    """The random draws of one training sample from the generator ``rng`` in ``__getitem__``'s order -- teacher theta, scale,
+    flip kind (with ``flip_aug``); the ``im_drop`` dropped cameras; student theta, scale -- as (teacher parameters, dropped
+    cameras, student parameters).  THE draw order of ``raw()`` and of every vote of ``raw_votes()``, on disk or synthetic."""
+    def rotation():
+        theta = rng.uniform(0, 2 * np.pi)
+        scale = rng.uniform(0.95, 1.05)
+        return np.array([[np.cos(theta), np.sin(theta), 0], [-np.sin(theta), np.cos(theta), 0], [0, 0, 1]]), float(scale)
+    teacher = {'rot': np.eye(3), 'scale': 1.0, 'flip': 0}
+    teacher['rot'], teacher['scale'] = rotation()
+    if flip_aug:
+        teacher['flip'] = int(rng.integers(0, 4))
+    drop = rng.choice(len(CAM_CHANNELS), im_drop, replace=False)
+    student = {}
+    student['rot'], student['scale'] = rotation()
+    return teacher, drop, student
 
 
 class LCNuScenesDataset(torch.utils.data.Dataset):
@@ -338,17 +356,47 @@ class LCNuScenesDataset(torch.utils.data.Dataset):
                 'tm': np.stack([tm for _, tm, _ in walked]).astype(np.float64) if walked else np.zeros((0, 4, 4)),
                 'lag': np.array([lag for _, _, lag in walked], dtype=np.float64)}
 
-    def _draw_rotation(self):
-        theta = self.rng.uniform(0, 2 * np.pi)
-        scale = self.rng.uniform(0.95, 1.05)
-        rot = np.array([[np.cos(theta), np.sin(theta), 0], [-np.sin(theta), np.cos(theta), 0], [0, 0, 1]])
-        return rot, float(scale)
-
     def raw(self, index):
         """What ``__getitem__(index)`` reads and draws, with none of its geometry done: the input of
         ``device_prep.prepare_kd_batch``.  ``self.rng`` is consumed in ``__getitem__``'s order (teacher theta, scale, flip
         kind; the dropped cameras; student theta, scale), so with equal seeds both describe the same sample.  numpy only: a
         loader worker that calls this never opens the device."""
+        if self.debug:                         # (before any draw: a refused call leaves the generator where it was)
+            raise NotImplementedError('raw(): debug (label_fov) is not served by the device path')
+        train = 'train' in self.split
+        teacher, drop, student = self._draw_sample() if train else self._identity_draws()
+        return self._raw_sample(index, train, teacher, drop, student)
+
+    @staticmethod
+    def _identity_draws():
+        return {'rot': np.eye(3), 'scale': 1.0, 'flip': 0}, [], {'rot': np.eye(3), 'scale': 1.0}
+
+    def _draw_sample(self):
+        """The random draws of one training sample in ``__getitem__``'s order: (teacher parameters, dropped cameras, student
+        parameters)."""
+        return draw_sample_parameters(self.rng, self.flip_aug, self.im_drop)
+
+    def raw_votes(self, index, num_vote):
+        """Test-time voting (``dataset.num_vote`` of the reference's evaluator): ``num_vote`` raw samples of scan ``index`` that
+        share every array by reference -- all cameras, labels as in the split (zeros for ``split='test'``).  Vote 0 carries
+        identity parameters; votes 1.. carry a rotation, scale and flip drawn from ``self.rng`` exactly as ``num_vote - 1``
+        training ``raw()`` calls draw them (the camera draw is made and not used, the student's yaw and scale are its own
+        draws).  All carry ``train=True``, the flag that makes ``u2mkd_prep_points`` apply the parameters: the identity leaves
+        every coordinate as it is."""
+        if num_vote < 1:
+            raise ValueError('raw_votes: num_vote >= 1, got %d' % num_vote)
+        if self.debug:
+            raise NotImplementedError('raw_votes(): debug (label_fov) is not served by the device path')
+        teacher, drop, student = self._identity_draws()
+        base = self._raw_sample(index, True, teacher, drop, student)
+        votes = [base]
+        for _ in range(1, num_vote):
+            teacher, _unused, student = self._draw_sample()
+            votes.append(dict(base, teacher=teacher, student=student))
+        return votes
+
+    def _raw_sample(self, index, train, teacher, drop, student):
+        """The files and tables of sample ``index`` around the given draws (``raw``, ``raw_votes``)."""
         if self.debug:
             raise NotImplementedError('raw(): debug (label_fov) is not served by the device path')
         nusc = self.nusc
@@ -361,20 +409,13 @@ class LCNuScenesDataset(torch.utils.data.Dataset):
         else:
             seg = np.fromfile(os.path.join(nusc.dataroot, nusc.get('lidarseg', lidar_token)['filename']), dtype=np.uint8)
             labels = _LABEL_LUT[seg]
-        train = 'train' in self.split
         sweeps = self._raw_sweeps(sample, self.multisweeps, self.only_past) if self.multisweeps != 0 else None
-        teacher = {'rot': np.eye(3), 'scale': 1.0, 'flip': 0}
-        if train:
-            teacher['rot'], teacher['scale'] = self._draw_rotation()
-            if self.flip_aug:
-                teacher['flip'] = int(self.rng.integers(0, 4))
-        drop = self.rng.choice(len(CAM_CHANNELS), self.im_drop, replace=False) if train else []
         cs_l = nusc.get('calibrated_sensor', lidar_sd['calibrated_sensor_token'])
         pose_l = nusc.get('ego_pose', lidar_sd['ego_pose_token'])
         f64 = lambda v: np.asarray(v, dtype=np.float64)
         cams, images = [], []
         for idx, channel in enumerate(CAM_CHANNELS):
-            if train and idx in drop:
+            if idx in drop:
                 continue
             cam_sd = nusc.get('sample_data', sample['data'][channel])
             im, (im_w, im_h) = self._load_image(os.path.join(nusc.dataroot, cam_sd['filename']))
@@ -384,9 +425,6 @@ class LCNuScenesDataset(torch.utils.data.Dataset):
             # lidar -> ego, ego -> global: p = R p + t; global -> ego (camera time), ego -> camera: p = R^T (p - t)
             steps = [(quat_to_rot(r['rotation']), f64(r['translation'])) for r in (cs_l, pose_l, pose_c, cs_c)]
             cams.append({'channel': idx, 'steps': steps, 'K': f64(cs_c['camera_intrinsic']), 'size': (im_w, im_h)})
-        student = {'rot': np.eye(3), 'scale': 1.0}
-        if train:
-            student['rot'], student['scale'] = self._draw_rotation()
         return {'points': np.ascontiguousarray(pts), 'labels': labels, 'sweeps': sweeps, 'teacher': teacher, 'student': student,
                 'cams': cams, 'images': np.stack(images, axis=0), 'voxel_size': self.voxel_size, 'train': train,
                 'multisweeps': self.multisweeps, 'ignore_index': self.ignored_labels, 'lidar_token': lidar_token}
@@ -410,6 +448,36 @@ class RawView(torch.utils.data.Dataset):
         return self.dataset.raw(index)
 
     collate_fn = staticmethod(lambda batch: raw_collate_fn(batch))
+
+
+class VoteBatch(list):
+    """Raw samples laid out scan-major -- copy v of scan s is item ``s * num_vote + v`` -- for ``device_prep``, which returns
+    the voting tables of such a batch (``evaluate.vote_point_predictions``)."""
+
+    def __init__(self, raws, num_vote):
+        super().__init__(raws)
+        if num_vote < 1 or len(self) % num_vote:
+            raise ValueError('VoteBatch: %d samples are not whole scans of %d votes' % (len(self), num_vote))
+        self.num_vote = int(num_vote)
+
+
+class VoteView(torch.utils.data.Dataset):
+    """``dataset`` served through ``raw_votes(index, num_vote)``: what the evaluator's DataLoader iterates; an item is the
+    list of a scan's copies, ``collate_fn`` lays the scans of a batch out as a ``VoteBatch``."""
+
+    def __init__(self, dataset, num_vote):
+        self.dataset, self.num_vote = dataset, int(num_vote)
+
+    rng = property(lambda self: self.dataset.rng, lambda self, v: setattr(self.dataset, 'rng', v))
+
+    def __len__(self):
+        return len(self.dataset)
+
+    def __getitem__(self, index):
+        return self.dataset.raw_votes(index, self.num_vote)
+
+    def collate_fn(self, batch):
+        return VoteBatch([copy for votes in batch for copy in votes], self.num_vote)
 
 
 def raw_collate_fn(batch):
